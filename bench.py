@@ -12,7 +12,16 @@ uniformly random dictIds; data is synthetic, generated on the host and resident 
 A step = one execution of the query over the rank's whole segment set: accumulator reset + the fused HIP scan
 kernel + (N>1) the RCCL reduce of partial aggregates to rank 0 + rank 0's fetch/decode of the groups.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the result line (value = rows/s over the timed steps,
+ms_per_step = one timed step). --full adds everything else the record holds, each outside the timed steps: the
+scan-kernel-only timing and its HBM roofline, the step with execution statistics, the secondary lines with their
+oracle checks, the CPU baseline and (N>1) the per-rank scan / merge times.
+
+--dump-outputs DIR writes what the last timed step returned to its caller (rank 0's results block) as DIR/<name>.npy,
+float64: group_keys [groups, group-by columns] in ascending key order, aggregates [groups, aggregations] in the same
+order, num_docs_scanned [1]. The segments are seeded, so the same arguments give the same inputs every run.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
        (N>1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
 """
 import argparse
@@ -209,6 +218,20 @@ def oracle_check(q, gsegs, host_segments, sptr):
             "check_groups": len(groups), "check_plan": plan["variant"], "check_dense_packed": plan["dense_packed"]}
 
 
+def dump_outputs(path, res):
+    """The results block of the last timed step as float64 arrays (every key, SUM and count here is below 2^53)."""
+    os.makedirs(path, exist_ok=True)
+    keys = sorted(res.groups)
+    arrays = {
+        "group_keys": np.array(keys, dtype=np.float64).reshape(len(keys), len(res.group_by)),
+        "aggregates": np.array([res.groups[k] for k in keys], dtype=np.float64).reshape(len(keys),
+                                                                                         len(res.aggregations)),
+        "num_docs_scanned": np.array([res.num_docs_scanned], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -218,12 +241,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--segments", type=int, default=100, help="segments per GPU")
     ap.add_argument("--docs", type=int, default=10_000_000, help="docs per segment")
-    ap.add_argument("--cpu-sample", type=int, default=16, help="segments in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: kernel-only timing and roofline, "
+                         "the step with execution statistics, the secondary lines, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results block to DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=16,
+                    help="segments in the CPU baseline sample (0 = skip); with --full")
     ap.add_argument("--flags", type=int, default=0)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the widened-IN-list secondary lines")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="skip the widened-IN-list secondary lines (with --full; a plain run has none)")
     ap.add_argument("--secondary", default="all",
                     help="run only this secondary line (sel_10pct | sel_50pct | sel_10pct_own_dicts | sel_50pct_own_dicts)")
     args = ap.parse_args()
+    # the host copies of the first segments serve the CPU baseline and the oracle checks only
+    cpu_sample = args.cpu_sample if args.full else 0
 
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -264,7 +296,7 @@ def main():
         if cids is None:
             cids = {n: j for j, n in enumerate(sorted(seg.columns))}
         gsegs.append(GpuSegment(seg, column_ids=cids, device=local))
-        if rank == 0 and len(host_sample) < args.cpu_sample:
+        if rank == 0 and len(host_sample) < cpu_sample:
             host_sample.append(seg)
         else:
             for c in seg.columns.values():  # HBM holds the forward index now; keep only the dictionaries
@@ -320,9 +352,12 @@ def main():
         return a.elapsed_time(b) / n
 
     # scan-kernel-only timing (per-launch duration = elapsed / steps, the figure rocprofv3 --stats averages)
+    # A plain run reports no kernel time but keeps these launches (steps x one scan, a few ms): the timed steps below have
+    # always started behind them, and without them the clocks are still ramping after a short --warmup, which reads
+    # ~1.5 % slower (0.424 against 0.418 ms per step at --steps 20 --warmup 5)
     kernel_ms = kernel_time(ex, args.steps)
     multi = None
-    if distributed:
+    if distributed and args.full:
         # per-rank evidence for a scaling record: each rank's scan time, the merge's time (the RCCL collective of the
         # partial aggregates alone, back to back) and the ranks the process group holds
         torch.cuda.synchronize()
@@ -350,19 +385,23 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    # the stats-inclusive step, timed the same way
-    for _ in range(max(1, args.warmup)):
-        sres = step_with_stats()
-    if distributed:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        sres = step_with_stats()
-    torch.cuda.synchronize()
-    if distributed:
-        dist.barrier()
-    elapsed_stats = time.perf_counter() - t1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    elapsed_stats, sres = 0.0, None
+    if args.full:
+        # the stats-inclusive step, timed the same way
+        for _ in range(max(1, args.warmup)):
+            sres = step_with_stats()
+        if distributed:
+            dist.barrier()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            sres = step_with_stats()
+        torch.cuda.synchronize()
+        if distributed:
+            dist.barrier()
+        elapsed_stats = time.perf_counter() - t1
     if distributed:
         t = torch.tensor([elapsed, elapsed_stats], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -379,7 +418,7 @@ def main():
             for i in mine:
                 seg = make_segment_own(5000 + i, args.docs, i)
                 own["g"].append(GpuSegment(seg, column_ids=cids, device=local))
-                if rank == 0 and len(own["host"]) < args.cpu_sample:
+                if rank == 0 and len(own["host"]) < cpu_sample:
                     own["host"].append(seg)
                 else:
                     for c in seg.columns.values():
@@ -388,7 +427,7 @@ def main():
             log("rank %d: own-dictionary segments resident, %.1f s" % (rank, time.perf_counter() - t))
         return own["g"], own["host"], own["kw"]
 
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         from pinot_amd import _lib as L
         lines = [(n, k, False) for n, k in SECONDARY] + [(n, k, True) for n, k in OWN_SECONDARY]
         for name, n_ids, own_dicts in lines:
@@ -424,11 +463,6 @@ def main():
     rows_per_gpu = st["num_docs"]
     total_rows = rows_per_gpu * world
     if rank == 0:
-        # algorithmic bytes (algorithmic_bytes): the staged accountId forward index + the sectors of the lazily read
-        # columns at the ~100 surviving docs
-        algo_bytes = algorithmic_bytes(ex, int(res.num_docs_scanned))
-        achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
-        cpu = cpu_baseline(q, host_sample) if host_sample else None
         out = {
             "metric": METRIC,
             "value": total_rows * args.steps / elapsed,
@@ -442,6 +476,7 @@ def main():
             "vs_baseline": None,
             "dtype": "int64",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": "adanalytics_readme_query",
                 "query": QUERY,
@@ -453,8 +488,15 @@ def main():
                 "parallelism": "segment-sharded dp%d, RCCL reduce of partial aggregates" % world,
                 "groups": len(res.groups) if res is not None else None,
                 "matched_docs_rank0": res.num_docs_scanned if res is not None else None,
+                "plan": st["plan"],
             },
-            "roofline": {
+        }
+        if args.full:
+            # algorithmic bytes (algorithmic_bytes): the staged accountId forward index + the sectors of the lazily read
+            # columns at the ~100 surviving docs
+            algo_bytes = algorithmic_bytes(ex, int(res.num_docs_scanned))
+            achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+            out["roofline"] = {
                 "bound": "hbm",
                 "achieved": achieved,
                 "peak": HBM_PEAK_GBS,
@@ -464,16 +506,15 @@ def main():
                 "kernel_ms": kernel_ms,
                 "algorithmic_bytes_per_launch": algo_bytes,
                 "plan": st["plan"],
-            },
-            "cpu_baseline": cpu,
+            }
+            out["cpu_baseline"] = cpu_baseline(q, host_sample) if host_sample else None
             # the same step with the execution statistics (numEntriesScannedInFilter of every segment: the scan's own
             # leap counts for this two-scan AND, pa_query_execution_stats)
-            "stats_step": {"ms_per_step": elapsed_stats * 1e3 / args.steps,
-                           "vs_plain_step": elapsed_stats / elapsed,
-                           "num_entries_scanned_in_filter_rank0": sres.num_entries_scanned_in_filter,
-                           "fused": int(L_lib().pa_query_leap_leaf(ex.handle)) >= 0},
-            "secondary": secondary,
-        }
+            out["stats_step"] = {"ms_per_step": elapsed_stats * 1e3 / args.steps,
+                                 "vs_plain_step": elapsed_stats / elapsed,
+                                 "num_entries_scanned_in_filter_rank0": sres.num_entries_scanned_in_filter,
+                                 "fused": int(L_lib().pa_query_leap_leaf(ex.handle)) >= 0}
+            out["secondary"] = secondary
         if multi is not None:
             out["multi_gpu"] = multi
         print(json.dumps(out), flush=True)

@@ -1,4 +1,4 @@
-"""Per-line rocprof summary of bench.py's secondary lines from one `rocprofv3 --kernel-trace` run of bench.py: the
+"""Per-line rocprof summary of bench.py's secondary lines from one `rocprofv3 --kernel-trace` run of bench.py --full: the
 gdl_jit dispatches in launch order, one block of (warmup + 1 + steps) per secondary line, next to the line's own
 HIP-event kernel_ms (bench.py's JSON line of the same run).
 
