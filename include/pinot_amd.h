@@ -52,7 +52,7 @@
 extern "C" {
 #endif
 
-#define PA_ABI_VERSION 4
+#define PA_ABI_VERSION 5
 
 /* limits of one query shape */
 #define PA_MAX_LEAVES 16
@@ -198,7 +198,7 @@ typedef struct {
 #define PA_QF_WG_SHIFT 12             /* bits 12..14: workgroups per CU (1..4) */
 #define PA_QF_NO_GDENSE_LM (1 << 15)      /* dense GROUP BY kernel: the step-major walk (ds_read2 per doc and column) instead
                                              of the lane-major one (each lane unpacks its 16 docs of every column) */
-#define PA_QF_NO_JIT (1u << 31)          /* never the query-shape specialised dense kernel (gdl_jit.hip); also PA_NO_JIT=1 */
+#define PA_QF_NO_JIT (1u << 31)          /* never the query-shape specialised dense kernel (gdl_jit.hip) */
 #define PA_QF_GD_DRAIN_EACH_TILE (1 << 2) /* testing: packed dense accumulation drains each wave's rows after every tile */
 #define PA_QF_NO_GD_PACK (1 << 3)         /* dense GROUP BY, lane-major walk: one LDS atomic per aggregation and matching doc
                                              instead of one packed word (COUNT + SUM terms) per matching doc */
@@ -258,6 +258,14 @@ int pa_query_bind_segment(pa_query* q, int32_t index, const pa_segment* seg,
  * dictId d (int32[segment cardinality]; NULL = identity, the segment's dictionary IS the table-wide one). Call after
  * pa_query_bind_segment, before pa_query_prepare. */
 int pa_query_bind_value_remap(pa_query* q, int32_t index, int32_t agg, const int32_t* remap);
+
+/* Tests and measurement only: overrides one planner decision of this query (the tunings, their ranges and defaults:
+ * pinot_amd/csrc/pa_tuning.h; the library reads none of them from the environment). Before pa_query_prepare.
+ * PA_EINVAL: unknown name, value outside the tuning's range, or query already prepared. */
+int pa_query_set_tuning(pa_query* q, const char* name, int32_t value);
+/* 1 when a tuning that skips work is set (results invalid: pa_query_fetch, pa_query_pack_rows and pa_query_merge_rows
+ * then fail; execute and scan still run, for timing), else 0; -1 for a null query. */
+int32_t pa_query_results_invalid(const pa_query* q);
 
 /* Uploads per-segment parameters, builds the tile schedule and HLL lookup tables, sizes the
  * accumulators. Must be called once after every segment is bound. */

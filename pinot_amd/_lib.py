@@ -50,14 +50,15 @@ PA_BIT_AND, PA_BIT_OR, PA_BIT_NOT = -1, -2, -3
 PA_BIT_PROG_MAX = 64
 PA_ACC_COUNT_U64, PA_ACC_SUM_I64, PA_ACC_SUM_F64, PA_ACC_MIN_I64, PA_ACC_MAX_I64, PA_ACC_HLL_U8, \
     PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8 = range(10)
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # every symbol declared in include/pinot_amd.h
 EXPORTED = [
     "pa_abi_version", "pa_device_count", "pa_set_device", "pa_last_error", "pa_host_alloc", "pa_host_free",
     "pa_segment_create", "pa_segment_add_sv_dict_column", "pa_segment_add_mv_dict_column",
     "pa_segment_add_raw_column", "pa_segment_num_docs", "pa_segment_device_bytes", "pa_segment_destroy",
-    "pa_query_create", "pa_query_bind_segment", "pa_query_bind_value_remap", "pa_query_prepare", "pa_query_num_keys",
+    "pa_query_create", "pa_query_set_tuning", "pa_query_results_invalid", "pa_query_bind_segment",
+    "pa_query_bind_value_remap", "pa_query_prepare", "pa_query_num_keys",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_partition_keys",
     "pa_query_accumulator_bytes", "pa_query_set_accumulator_buffer", "pa_query_num_sections", "pa_query_section",
@@ -135,6 +136,8 @@ def _declare(lib):
         "pa_segment_device_bytes": (u64, [vp]),
         "pa_segment_destroy": (None, [vp]),
         "pa_query_create": (vp, [ctypes.POINTER(QuerySpec), i32]),
+        "pa_query_set_tuning": (ctypes.c_int, [vp, ctypes.c_char_p, i32]),
+        "pa_query_results_invalid": (i32, [vp]),
         "pa_query_bind_segment": (ctypes.c_int, [vp, i32, vp, ctypes.POINTER(LeafParams), vp]),
         "pa_query_bind_value_remap": (ctypes.c_int, [vp, i32, i32, vp]),
         "pa_query_prepare": (ctypes.c_int, [vp]),

@@ -60,7 +60,7 @@ typedef __attribute__((address_space(3))) u64 l64;
 #define JIT_SEGDRAIN 0  // the rows are drained at every segment switch (their local keys / offsets change there)
 #endif
 #ifndef JIT_DBG
-#define JIT_DBG 0  // measurement only (PA_GDL_DBG; results invalid): 1 = stream the tiles only, 2 = + the filter,
+#define JIT_DBG 0  // measurement only (tuning gdl_dbg; results invalid): 1 = stream the tiles only, 2 = + the filter,
 #endif             // 3 = + keys and packed terms (no row atomics)
 #ifndef JIT_RING
 #define JIT_RING 2  // tile images per wave: JIT_RING - 1 tiles in flight while one is walked

@@ -28,6 +28,20 @@ pa_query* pa_query_create(const pa_query_spec* spec, int32_t num_segments) {
   return q;
 }
 
+int pa_query_set_tuning(pa_query* q, const char* name, int32_t value) {
+  if (!q) return fail(PA_EINVAL, "null query");
+  if (q->prepared) return fail(PA_EINVAL, "query already prepared");
+  const TuningDef* d = tuning_named(name);
+  if (!d) return fail(PA_EINVAL, std::string("unknown tuning: ") + (name ? name : "(null)"));
+  if (value != d->def && (value < d->lo || value > d->hi))
+    return fail(PA_EINVAL, std::string("tuning ") + d->name + ": " + std::to_string(value) + " outside " +
+                               std::to_string(d->lo) + ".." + std::to_string(d->hi));
+  q->tune.*d->value = value;
+  return PA_OK;
+}
+
+int32_t pa_query_results_invalid(const pa_query* q) { return q ? (tuning_invalidating(q->tune) ? 1 : 0) : -1; }
+
 int pa_query_bind_segment(pa_query* q, int32_t index, const pa_segment* seg, const pa_leaf_params* leaf_params,
                           const int32_t* const* group_remaps) {
   if (!q || !seg || index < 0 || index >= q->nseg) return fail(PA_EINVAL, "bad bind arguments");
@@ -223,7 +237,7 @@ int pa_query_scan(pa_query* q, void* stream) {
   if (q->limit_walk) {  // admitted keys of every segment where the limit can bind, before any pass tests them
     if (q->walk_words > kWalkMaxWords) PA_HIP(hipMemsetAsync(q->lim_admit.p, 0, q->lim_admit.n, st));
     PA_HIP(launch_limit_walk((const DevQuery*)q->dq.p, (const DevSeg*)q->dsegs.p, q->nseg, q->walk_words,
-                             q->hq.gb_mv >= 0, st));
+                             q->hq.gb_mv >= 0, q->tune.walk_tab != 0, st));
   }
   if (q->limit_mode) {  // first-seen positions, per-segment selection of the threshold, admitted aggregation
     const DevQuery* dq = (const DevQuery*)q->dq.p;
@@ -270,7 +284,7 @@ int pa_query_scan(pa_query* q, void* stream) {
       }
     }
     PA_HIP(launch_part_agg(q->part_vk, (const DevQuery*)q->dq.p, ps, q->pvh.fn ? q->hq.num_parts : q->hq.pv,
-                           q->hq.pv, q->hq.v_fmt <= V_FMT_ID, q->part_lds_c, st));
+                           q->hq.pv, q->hq.v_fmt <= V_FMT_ID, q->tune.passc_v16, q->part_lds_c, st));
     return PA_OK;
   }
   if (q->partitioned) {  // count pass, range offsets, emit pass into the partitions, per-partition aggregation
@@ -290,7 +304,7 @@ int pa_query_scan(pa_query* q, void* stream) {
       PA_HIP(launch_scan(q->emit_h_strat, q->steps, 0, q->grid, q->emit_h_lds, (const DevQuery*)q->dq_h.p,
                          (const DevSeg*)q->dsegs.p, plans, ps, st));
     PA_HIP(launch_part_agg(q->part_vk, (const DevQuery*)q->dq.p, ps, q->hq.num_parts, q->hq.pv, q->hq.v_fmt <= V_FMT_ID,
-                           q->part_lds_c, st));
+                           q->tune.passc_v16, q->part_lds_c, st));
     PA_HIP(hipEventRecord(a->last, st));
     a->last_stream = st;
     a->used = true;

@@ -265,7 +265,7 @@ struct DevQuery {
   int32_t gb_mv;             // the multi-value group-by component (V records: one per (doc, value) pair), -1: none
   int32_t count_skip_gb;     // count pass: a group-by component that cannot change a key's partition (not staged), -1
   int32_t part_lo, part_hi;   // emit pass: the partitions this launch emits ([0, pv) V, [pv, P) H, or all)
-  int32_t debug_emit;        // measurement only (PA_DEBUG_EMIT): bit 0 skips the emit pass's record stores, bit 1 its HLL
+  int32_t debug_emit;        // measurement only (tuning debug_emit): bit 0 skips the emit pass's record stores, bit 1 its HLL
                              // dictionary gathers, bit 2 its MV value reads (wrong results; isolates the waits)
   uint32_t lds_cnt, lds_done, lds_front, lds_back, lds_start;  // STRAT_PEMIT LDS (bytes): per-partition bin state
   uint32_t lds_slack, pad_slack;  // STRAT_PEMIT LDS (bytes): per-partition parked tail of an H bin

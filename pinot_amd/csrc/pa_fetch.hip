@@ -2,10 +2,17 @@
 // pack / merge for the cross-GPU exchange.
 #include "pa_host.h"
 
+// A query whose tunings skip work in a kernel (pa_query_results_invalid) can be executed and timed, not read
+static int refuse_invalid(const pa_query* q) {
+  const char* t = tuning_invalidating(q->tune);
+  return t ? fail(PA_EINVAL, std::string("results invalid: tuning ") + t + " is set") : PA_OK;
+}
+
 extern "C" {
 int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out_keys, int64_t* out_counts,
                        void* const* out_aggs) {
   if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
+  if (int rc = refuse_invalid(q)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const pa_query_spec& s = q->spec;
   const int64_t K = q->num_keys;
@@ -274,8 +281,9 @@ int64_t pa_query_row_bytes(const pa_query* q) {
 int pa_query_pack_rows(pa_query* q, int32_t world, void* device_rows, int64_t* counts, void* stream) {
   RowDesc d;
   int rc = row_desc(q, d);
+  if (!rc) rc = refuse_invalid(q);
   if (rc) return rc;
-  if (world < 1 || world > 1024 || !counts) return fail(PA_EINVAL, "pack rows: bad world size or null counts");
+  if (world < 1|| world > 1024 || !counts) return fail(PA_EINVAL, "pack rows: bad world size or null counts");
   hipStream_t st = (hipStream_t)stream;
   // scratch: counts[world], cursor[world], row_slot[num_slots]
   rc = merge_scratch(q, (size_t)(2 * world + d.num_slots) * 8);
@@ -307,8 +315,9 @@ int pa_query_merge_rows(pa_query* q, const void* device_rows, int64_t num_rows, 
                         void* stream) {
   RowDesc d;
   int rc = row_desc(q, d);
+  if (!rc) rc = refuse_invalid(q);
   if (rc) return rc;
-  if (num_rows < 0 || (num_rows > 0 && !device_rows)) return fail(PA_EINVAL, "merge rows: bad rows");
+  if (num_rows < 0|| (num_rows > 0 && !device_rows)) return fail(PA_EINVAL, "merge rows: bad rows");
   hipStream_t st = (hipStream_t)stream;
   rc = merge_scratch(q, (size_t)(8 + std::max<int64_t>(num_rows, d.num_slots)) * 8);
   if (rc) return rc;

@@ -107,7 +107,7 @@ __device__ __forceinline__ void gd_batch(uint32_t gt, const GdLane<MG, MA>& L, c
                                          uint32_t r, uint32_t base, uint32_t& errs) {
   const int ngb = (int)rl(gt, 0), na = (int)rl(gt, 1);
   const uint32_t rpl = rl(gt, 2);
-  const uint32_t dbg = rl(gt, 3);  // measurement only (PA_DEBUG_EMIT): 2 = no atomics, 4 = no value-table reads
+  const uint32_t dbg = rl(gt, 3);  // measurement only (tuning debug_emit): 2 = no atomics, 4 = no value-table reads
   uint32_t key[N];
   bool on[N];
 #pragma unroll
@@ -742,7 +742,7 @@ template <int MG = kGdMaxGb, int MA = kGdMaxAgg>
 __device__ __forceinline__ uint32_t gdl_tile(uint32_t gt, uint32_t lp, int64_t wt, uint32_t img, int lane,
                                              uint32_t base, uint32_t rows, uint32_t& errs) {
   constexpr int ND = kGdlDocs;
-  const uint32_t dbg = rl(gt, 3);  // measurement only (PA_DEBUG_EMIT): 32 stream only, 1 filter only, 2 no atomics
+  const uint32_t dbg = rl(gt, 3);  // measurement only (tuning debug_emit): 32 stream only, 1 filter only, 2 no atomics
   if (dbg & 32) return 0;
   const int64_t rem = (int64_t)(int32_t)rl(lp, 1) - wt * (kGdSmSteps * kWave);
   uint32_t m = 0xffffu;
@@ -1222,7 +1222,7 @@ __global__ void __launch_bounds__(WPW * kWave, 1) gdense_kernel(const DevQuery* 
       }
       for (; t < send; t += WPW) {
         uint32_t slot_off = (uint32_t)(pslot * img_dw);
-        if (LM == 2 && (rl(gt, 3) & 64)) {  // measurement only (PA_DEBUG_EMIT 64): no DMA, compute on stale images
+        if (LM == 2 && (rl(gt, 3) & 64)) {  // measurement only (tuning debug_emit 64): no DMA, compute on stale images
           ti = t1;
         } else {
           if (LM == 2 && R == 2) vm_wait<0>();  // (two images: the one tile in flight is this one)

@@ -24,6 +24,7 @@
 #include "pa_device.h"
 #include "pa_launch.h"
 #include "pa_jit_abi.h"
+#include "pa_tuning.h"
 
 using namespace pa;
 
@@ -35,14 +36,17 @@ inline int fail(int code, const std::string& msg) {
   return code;
 }
 
-// PA_DEBUG_PLAN=1: the planner's decisions on stderr (why a query takes a strategy)
-inline bool plan_debug() {
-  static const bool on = std::getenv("PA_DEBUG_PLAN") != nullptr;
-  return on;
+// The two environment variables the library reads; both only log to stderr. PA_DEBUG_PLAN=1: the planner's decisions
+// (why a query takes a strategy); PA_JIT_LOG=1: hiprtc's log when a query-shape kernel fails to compile. Everything that
+// changes a plan or a result is a flag of the query spec or a tuning the query carries (pa_tuning.h).
+enum { LOG_PLAN = 1, LOG_JIT = 2 };
+inline bool log_on(int what) {
+  static const int on = (std::getenv("PA_DEBUG_PLAN") ? LOG_PLAN : 0) | (std::getenv("PA_JIT_LOG") ? LOG_JIT : 0);
+  return (on & what) != 0;
 }
 #define PLAN_LOG(...)                                  \
   do {                                                 \
-    if (plan_debug()) {                                \
+    if (log_on(LOG_PLAN)) {                            \
       std::fprintf(stderr, "[pa plan] " __VA_ARGS__); \
       std::fputc('\n', stderr);                       \
     }                                                  \
@@ -199,6 +203,7 @@ struct pa_query {
   std::vector<std::vector<std::vector<int32_t>>> vremaps;      // [seg][agg] DISTINCTCOUNT value remaps (empty = identity)
   std::vector<std::vector<int32_t>> vremap_host;               // [seg] host copy of DevSeg::vremap (value_dictionary)
   bool prepared = false;
+  Tuning tune;  // planner overrides (pa_query_set_tuning: tests and measurement)
 
   // plan
   std::vector<int32_t> slot_cols;

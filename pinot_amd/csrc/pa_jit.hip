@@ -6,7 +6,7 @@
 // The lane-major dense kernel with packed accumulation, compiled per query shape by hiprtc: every column width, image
 // offset, leaf kind and field offset becomes a constant (no bit-width switch, no parameter reads, no DMA loop in the
 // tile loop). Compiled once per shape and device and cached for the process; the generic kernel runs when the shape
-// is outside the specialised form (or PA_QF_NO_JIT / PA_NO_JIT), or hiprtc fails.
+// is outside the specialised form (or PA_QF_NO_JIT), or hiprtc fails.
 static const char* kGdlJitSrc =
 #include "gdl_jit_src.inc"
     ;
@@ -52,7 +52,7 @@ hipFunction_t jit_compile(const std::vector<std::string>& defs, const char* src 
         g_jit_cache[key] = e;
       }
     }
-  } else if (std::getenv("PA_JIT_LOG")) {
+  } else if (log_on(LOG_JIT)) {
     size_t n = 0;
     hiprtcGetProgramLogSize(prog, &n);
     std::vector<char> log(n + 1, 0);
@@ -111,7 +111,8 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
   if (q->nseg == 0 || s.num_group_by != 1 || !P.gd_box_ok || P.gd_box || q->hq.leap_mode || q->partitioned ||
       q->limit_mode || q->limit_walk || q->hashed)
     return PA_OK;
-  if ((s.flags & PA_QF_NO_JIT) || std::getenv("PA_NO_JIT") || std::getenv("PA_DEBUG_EMIT")) return PA_OK;
+  const Tuning& tn = q->tune;
+  if ((s.flags & PA_QF_NO_JIT) || tn.debug_emit) return PA_OK;
   // flags that pin a generic plan (tests and measurement) keep it
   if (s.flags & (PA_QF_NO_DENSE_GROUP | PA_QF_FORCE_GLOBAL | PA_QF_FORCE_LDS | PA_QF_LAZY_POST | PA_QF_NO_LANE_MAJOR |
                  PA_QF_STEPS16 | PA_QF_DEBUG_STREAM_ONLY | PA_QF_NO_GDENSE_LM | PA_QF_NO_GD_PACK))
@@ -376,7 +377,7 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
   }
   const size_t l_slot = off, slot_b = al16(so);
   // waves, docs per lane and waves per set of packed rows: the most resident waves, then the larger tile, then private
-  // rows (PA_GDL_W / PA_GDL_ND / PA_GDL_RS: measurement)
+  // rows (tunings gdl_w / gdl_nd / gdl_rs keep only the candidates with their value)
   struct Cand {
     int w, nd, rs;
   };
@@ -384,15 +385,13 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
   // ms; 8 waves of 1024-doc tiles beat 12 of 512: shared 1.391 vs 1.425 ms; 12 of 512 beat 8 of 512: 1.425 vs 1.594 ms)
   std::vector<Cand> cands = {{16, 16, 1}, {12, 16, 1}, {16, 8, 1}, {8, 16, 1}, {12, 8, 1}, {8, 8, 1}, {16, 16, 2},
                              {16, 8, 2}};
-  auto keep_only = [&](const char* env, int Cand::*f) {
-    if (const char* e = std::getenv(env)) {
-      const int v = std::atoi(e);
+  auto keep_only = [&](int v, int Cand::*f) {
+    if (v >= 0)
       cands.erase(std::remove_if(cands.begin(), cands.end(), [&](const Cand& c) { return c.*f != v; }), cands.end());
-    }
   };
-  keep_only("PA_GDL_W", &Cand::w);
-  keep_only("PA_GDL_ND", &Cand::nd);
-  keep_only("PA_GDL_RS", &Cand::rs);
+  keep_only(tn.gdl_w, &Cand::w);
+  keep_only(tn.gdl_nd, &Cand::nd);
+  keep_only(tn.gdl_rs, &Cand::rs);
   bool any_offs = false;  // (per-segment SUM offsets are folded in at the drain: one segment per private row set)
   for (const JitSum& J : sums) any_offs |= !J.table && J.offs;
   // the packed rows are indexed by each segment's local keys: its keys inside the box, [lbase, lbase + lspan) of its
@@ -417,9 +416,8 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
   }
   if (any_offs || segdrain)
     cands.erase(std::remove_if(cands.begin(), cands.end(), [](const Cand& c) { return c.rs != 1; }), cands.end());
-  // tile images per wave (PA_GDL_RING: measurement): RING - 1 tiles in flight while one is walked
-  int ring_n = 2;
-  if (const char* e = std::getenv("PA_GDL_RING")) ring_n = std::max(2, std::min(4, std::atoi(e)));
+  // tile images per wave: RING - 1 tiles in flight while one is walked
+  const int ring_n = tn.gdl_ring >= 0 ? tn.gdl_ring : 2;
   int W = 0, ND = 0, RS = 1, RR = 1, nslot = 0, G = 0, img_dw = 0;
   size_t lds = 0, l_rows = 0, l_ring = 0;
   std::vector<int64_t> first(ni + 1, 0);
@@ -455,9 +453,8 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
     const size_t rows = al16(l_slot + (size_t)ns * slot_b);
     const size_t ring_img = (size_t)w * ring_n * idw * 4;
     // row replicas: as many as fit (up to one per lane), so the lanes of a wave hitting a segment's few keys update
-    // different words (PA_GDL_RR: measurement)
-    int rr = 64;
-    if (const char* e = std::getenv("PA_GDL_RR")) rr = std::max(1, std::min(64, std::atoi(e)));
+    // different words
+    int rr = tn.gdl_rr >= 0 ? tn.gdl_rr : 64;
     while (rr > 1 && al16(rows + (size_t)(w / cd.rs) * lmax * rr * 8) + ring_img > kLdsBudget) rr >>= 1;
     while (rr > 1 && (rr & (rr - 1))) rr &= rr - 1;
     const size_t ring = al16(rows + (size_t)(w / cd.rs) * lmax * rr * 8);
@@ -521,7 +518,7 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
       "-DJIT_L_RING=" + std::to_string(l_ring), "-DJIT_RS=" + std::to_string(RS), "-DJIT_RR=" + std::to_string(RR),
       "-DJIT_LMAX=" + std::to_string(lmax), "-DJIT_SEGDRAIN=" + std::to_string(segdrain ? 1 : 0),
       "-DJIT_RING=" + std::to_string(ring_n)};
-  if (const char* dbg = std::getenv("PA_GDL_DBG")) defs.push_back(std::string("-DJIT_DBG=") + dbg);  // (measurement)
+  if (tn.gdl_dbg) defs.push_back("-DJIT_DBG=" + std::to_string(tn.gdl_dbg));
   hipFunction_t fn = jit_compile(defs);
   if (!fn) return PA_OK;
   (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -726,7 +723,8 @@ static int pve_stream(pa_query* q, const Prep& P, int cus, bool hmode, int rw, i
   if (Pn < 1 || Pn > 4096 || ks < 1) return PA_OK;
   // tile image of nd docs per lane (64 nd per tile): a 16-byte guard, then per column its tile's bits (8 nd nb bytes)
   // and a 16-byte guard, then the raw values (64 nd rawb bytes). 16 docs per lane unless 8 leave room for more
-  // resident waves (PA_PVE_ND: measurement); 32-record bins unless 16 do (H: many partitions)
+  // resident waves; 32-record bins unless 16 do (H: many partitions). The pve_* tunings override each choice
+  const Tuning& tn = q->tune;
   auto al16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
   auto image_bytes = [&](int nd) {
     size_t b = 16;
@@ -740,22 +738,15 @@ static int pve_stream(pa_query* q, const Prep& P, int cus, bool hmode, int rw, i
     return hmode ? (size_t)16 * (((size_t)max_values * 64 * nd * hnb / 32 + 17 + 3) / 4) : (size_t)0;
   };
   // H run rounds: one claim per run of up to hb values of one doc (its values share the doc's key); hb = the column's
-  // most values per doc up to 8, so a run is normally a whole doc. PA_PVE_HRUN=0 keeps one claim per value
-  // (measurement), PA_PVE_HB sets the run length
-  bool hrun = true;
-  if (const char* e = std::getenv("PA_PVE_HRUN")) hrun = std::atoi(e) != 0;
-  int hb = (int)std::max<int64_t>(1, std::min<int64_t>(8, max_values));
-  if (const char* e = std::getenv("PA_PVE_HB")) hb = std::max(1, std::min(8, std::atoi(e)));
-  // tile images per wave (PA_PVE_RING: measurement; the H stream and admission loads keep two)
-  int rn = 2;
-  if (const char* e = std::getenv("PA_PVE_RING")) rn = std::max(2, std::min(4, std::atoi(e)));
-  if (hmode || q->limit_walk) rn = 2;
+  // most values per doc up to 8, so a run is normally a whole doc
+  const bool hrun = tn.pve_hrun != 0;
+  const int hb = tn.pve_hb >= 0 ? tn.pve_hb : (int)std::max<int64_t>(1, std::min<int64_t>(8, max_values));
+  // tile images per wave (the H stream and admission loads keep two)
+  const int rn = (tn.pve_ring >= 0 && !hmode && !q->limit_walk) ? tn.pve_ring : 2;
   // compacted put rounds: a queue of 512 records (partition + record words) per wave, for a V stream whose filter is
   // expected to keep less than half the docs (configs[2] 10 %: 0.409 vs 0.496 ms per 200M docs; on every doc it costs
-  // resident waves: 1.38 vs 1.20 ms, and the H stream's uneven MV runs gain nothing: 5.26 vs 3.89 ms). PA_PVE_Q=0 / 1
-  // forces it (measurement)
-  bool pq = !hmode && P.has_filter && P.post_density < 0.5 * (double)kWTileDocs;
-  if (const char* e = std::getenv("PA_PVE_Q")) pq = std::atoi(e) != 0;
+  // resident waves: 1.38 vs 1.20 ms, and the H stream's uneven MV runs gain nothing: 5.26 vs 3.89 ms)
+  const bool pq = tn.pve_q >= 0 ? tn.pve_q != 0 : !hmode && P.has_filter && P.post_density < 0.5 * (double)kWTileDocs;
   const size_t qbytes = pq ? (size_t)4 * 512 * (rw + 1) : 0;
   auto waves_for = [&](int nd, int bs) {
     for (int cand : {16, 12, 8, 4})
@@ -768,8 +759,8 @@ static int pve_stream(pa_query* q, const Prep& P, int cus, bool hmode, int rw, i
   int bs = 32;
   if (waves_for(8, 32) < 8 && waves_for(8, 16) > waves_for(8, 32)) bs = 16;
   int nd = hmode ? 8 : (waves_for(8, bs) > waves_for(16, bs) ? 8 : 16);
-  if (const char* e = std::getenv("PA_PVE_ND")) nd = std::atoi(e) == 8 ? 8 : 16;
-  if (const char* e = std::getenv("PA_PVE_BS")) bs = std::atoi(e) == 16 ? 16 : 32;  // (measurement)
+  if (tn.pve_nd >= 0) nd = tn.pve_nd == 8 ? 8 : 16;
+  if (tn.pve_bs >= 0) bs = tn.pve_bs == 16 ? 16 : 32;
   const int w = waves_for(nd, bs);
   if (!w) return PA_OK;
   std::vector<int> nb, coff;
@@ -796,13 +787,12 @@ static int pve_stream(pa_query* q, const Prep& P, int cus, bool hmode, int rw, i
   const int64_t T = first[q->nseg];
   const int G = (int)std::max<int64_t>(1, std::min<int64_t>(cus, (T + w - 1) / w));
   const int64_t recs_per_wg = (T + G - 1) / G * td * (int64_t)max_values;
-  // chunks of 8 bins (4: configs[2] 1.215 vs 1.192 ms, configs[4] 7.49 vs 7.40 ms; PA_PVE_SC: measurement)
-  int sc = std::getenv("PA_PVE_SC") ? std::atoi(std::getenv("PA_PVE_SC")) : 8;
-  if (sc < 1 || sc > 16 || (sc & (sc - 1))) return PA_OK;  // (bins - 1 of a chunk: 4 bits of its list entry)
+  // chunks of 8 bins (4: configs[2] 1.215 vs 1.192 ms, configs[4] 7.49 vs 7.40 ms), at most 16 (bins - 1 of a chunk:
+  // 4 bits of its list entry)
+  int sc = 8;
   auto chunks_for = [&](int c) { return (recs_per_wg + (int64_t)bs * c - 1) / ((int64_t)bs * c) + Pn; };
   while (sc < 16 && chunks_for(sc) >= (int64_t(1) << 16)) sc *= 2;
-  const int64_t cr = (int64_t)bs * sc;  // records per chunk
-  if (cr < 64) return PA_OK;             // (pass C: a wave's 64 records of one slot lie in one chunk)
+  const int64_t cr = (int64_t)bs * sc;  // records per chunk (>= 128; pass C: a wave's 64 records of one slot lie in one)
   const int64_t C = chunks_for(sc);
   if (C >= (int64_t(1) << 16) || (int64_t)G * C >= (int64_t(1) << 28)) return PA_OK;  // (table ranks, chunk ids)
   auto pad1 = [](std::vector<int> v) {
@@ -828,9 +818,7 @@ static int pve_stream(pa_query* q, const Prep& P, int cus, bool hmode, int rw, i
       "-DPVE_KR=" + std::to_string(hmode ? 0 : h.part_kr_v), "-DPVE_RING=" + std::to_string(rn), "-DPVE_Q=" + std::to_string(pq ? 1 : 0),
       "-DPVE_L_Q=" + std::to_string(l_q), "-DPVE_HRUN=" + std::to_string(hmode && hrun ? 1 : 0),
       "-DPVE_HB=" + std::to_string(hb)};
-  if (const char* dbg = std::getenv("PA_PVE_DBG")) defs.push_back(std::string("-DPVE_DBG=") + dbg);  // (measurement)
-  if (const char* pb = std::getenv("PA_PVE_PB")) defs.push_back(std::string("-DPVE_PB=") + pb);      // (measurement)
-  if (std::getenv("PA_PVE_DONE_RTN")) defs.push_back("-DPVE_DONE_RTN=1");                            // (measurement)
+  if (tn.pve_dbg) defs.push_back("-DPVE_DBG=" + std::to_string(tn.pve_dbg));
   hipFunction_t fn = jit_compile(defs, kPveJitSrc, "pve_jit");
   if (!fn) return PA_OK;
   (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -909,7 +897,7 @@ static int pve_stream(pa_query* q, const Prep& P, int cus, bool hmode, int rw, i
 static bool pve_repartition(pa_query* q, const Prep& P, int cus) {
   DevQuery& h = q->hq;
   const pa_query_spec& s = q->spec;
-  if (h.hll_agg >= 0 || h.pv <= cus || std::getenv("PA_PVE_POW2")) return false;  // (PA_PVE_POW2: measurement)
+  if (h.hll_agg >= 0 || h.pv <= cus) return false;
   size_t per_key = 4;  // pass C's LDS per key: u32 count, then each aggregation's slot
   for (int a = 0; a < s.num_aggs; ++a) {
     const int t = s.aggs[a].type;
@@ -949,9 +937,8 @@ int pve_plan(pa_query* q, const Prep& P, int cus) {
   const DevQuery& h = q->hq;
   if (!q->partitioned || q->limit_mode || q->hashed) return PA_OK;
   if (q->limit_walk && h.gb_mv >= 0) return PA_OK;
-  if ((s.flags & PA_QF_NO_JIT) || (s.flags2 & PA_QF2_NO_COUNT_FREE) || std::getenv("PA_NO_JIT") ||
-      (std::getenv("PA_DEBUG_EMIT") && !std::getenv("PA_PVE_DBG")))
-    return PA_OK;
+  if ((s.flags & PA_QF_NO_JIT) || (s.flags2 & PA_QF2_NO_COUNT_FREE)) return PA_OK;
+  if (q->tune.debug_emit && !q->tune.pve_dbg) return PA_OK;  // (debug_emit keeps the count + emit passes it instruments)
   // both streams (DISTINCTCOUNTHLLMV next to a V stream): two launches, COUNT from the V records
   const bool hstream = h.hll_agg >= 0;
   if (hstream && (!q->split_emit || h.h_first || h.gb_mv >= 0)) return PA_OK;

@@ -558,13 +558,10 @@ __global__ void __launch_bounds__(kWalkThreads) limit_walk_mv_kernel(const DevQu
   if (reached && tid == 0) __hip_atomic_fetch_add(gp(q->matched_docs) + 2, 1ull, RLX);  // numGroupsLimitReached
 }
 
-hipError_t launch_limit_walk(const DevQuery* q, const DevSeg* segs, int nseg, int64_t words, bool mv, hipStream_t s) {
-  // the replay's first-lane table: up to 4096 words in what the bitmap leaves of the LDS (PA_WALK_TAB=0: none,
-  // measurement)
-  static const bool use_tab = [] {
-    const char* e = std::getenv("PA_WALK_TAB");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
+hipError_t launch_limit_walk(const DevQuery* q, const DevSeg* segs, int nseg, int64_t words, bool mv, bool use_tab,
+                             hipStream_t s) {
+  // the replay's first-lane table: up to 4096 words in what the bitmap leaves of the LDS (use_tab false: none, the
+  // walk_tab tuning)
   auto tlog_for = [&](size_t used) {
     int t = 0;
     if (use_tab)
@@ -1680,7 +1677,7 @@ __device__ void part_agg_v_fast(const DevQuery* __restrict__ q, const PartScratc
   }
 }
 
-template <int NT = kPartAggThreads, int KB = 8>
+template <int NT, int KB>
 __device__ void part_agg_h(const DevQuery* __restrict__ q, const PartScratch& ps, int ph, unsigned char* lds) {
   const DevAgg& H = q->aggs[q->hll_agg];
   const int lg = H.log2m;
@@ -1783,43 +1780,25 @@ __device__ void part_agg_h(const DevQuery* __restrict__ q, const PartScratch& ps
 template <int VK>
 __global__ void __launch_bounds__(kPartAggThreads) part_agg_kernel(const DevQuery* __restrict__ q, PartScratch ps) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  if ((int)blockIdx.x < q->pv) {
-    if constexpr (VK == kVkGeneric) part_agg_v(q, ps, (int)blockIdx.x, (unsigned char*)smem);
-    else part_agg_v_fast<VK>(q, ps, (int)blockIdx.x, (unsigned char*)smem);
-  } else {
-    part_agg_h(q, ps, (int)blockIdx.x - q->pv, (unsigned char*)smem);
-  }
+  if constexpr (VK == kVkGeneric) part_agg_v(q, ps, (int)blockIdx.x, (unsigned char*)smem);
+  else part_agg_v_fast<VK>(q, ps, (int)blockIdx.x, (unsigned char*)smem);
 }
 
-// H partitions alone, 16 waves per workgroup: a partition's registers fill the LDS (one workgroup per CU), and with 8
-// waves each wave's record loads and LDS round trips sat exposed (the V variants' registers do not fit 16 waves)
+// The H partitions have their own launch at 16 waves per workgroup: a partition's registers fill the LDS (one workgroup
+// per CU), and with 8 waves each wave's record loads and LDS round trips sat exposed (the V variants' registers do not
+// fit 16 waves). 16 records per thread in flight (8: 990 vs 960 us on configs[4])
 constexpr int kPartAggHThreads = 1024;
-template <int KB>
 __global__ void __launch_bounds__(kPartAggHThreads) part_agg_h_kernel(const DevQuery* __restrict__ q, PartScratch ps) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
-  part_agg_h<kPartAggHThreads, KB>(q, ps, (int)blockIdx.x, (unsigned char*)smem);
-}
-static const void* part_agg_h_fn() {  // 16 records per thread in flight (8: 990 vs 960 us on configs[4]; PA_PASSC_HKB)
-  static const bool b16 = [] {
-    const char* e = std::getenv("PA_PASSC_HKB");
-    return e == nullptr || std::atoi(e) != 8;
-  }();
-  return b16 ? (const void*)part_agg_h_kernel<16> : (const void*)part_agg_h_kernel<8>;
+  part_agg_h<kPartAggHThreads, 16>(q, ps, (int)blockIdx.x, (unsigned char*)smem);
 }
 // V partitions at 16 waves per workgroup, one register batch per wave: for one-word records (configs[2]: pass C 505 ->
 // 364 us, the all-docs line 1.185 -> 1.069 ms); 3-word raw-value records stay at 8 waves with two batches (configs[4]:
-// 775 vs 735 us). PA_PASSC_V16=0 / 1 forces it (measurement)
+// 775 vs 735 us). The passc_v16 tuning forces either
 template <int VK>
 __global__ void __launch_bounds__(kPartAggHThreads) part_agg_v16_kernel(const DevQuery* __restrict__ q, PartScratch ps) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   part_agg_v_fast<VK, kPartAggHThreads>(q, ps, (int)blockIdx.x, (unsigned char*)smem);
-}
-static bool part_agg_v16(bool one_word) {
-  static const int force = [] {
-    const char* e = std::getenv("PA_PASSC_V16");
-    return e == nullptr ? -1 : (std::atoi(e) != 0 ? 1 : 0);
-  }();
-  return force < 0 ? one_word : force != 0;
 }
 static const void* part_agg_v16_variant(int vk) {
   switch (vk) {
@@ -1830,14 +1809,6 @@ static const void* part_agg_v16_variant(int vk) {
     default: return nullptr;
   }
 }
-static bool part_agg_h_split() {
-  static const bool on = [] {
-    const char* e = std::getenv("PA_PASSC_H_SPLIT");  // (measurement: 0 = H partitions in the V launch, 8 waves)
-    return e == nullptr || std::atoi(e) != 0;
-  }();
-  return on;
-}
-
 template <int VK>
 static const void* part_agg_fn() { return (const void*)part_agg_kernel<VK>; }
 static const void* part_agg_variant(int vk) {
@@ -1859,7 +1830,8 @@ hipError_t launch_part_offsets(const DevQuery* hq, const PartScratch& ps, int G,
 }
 
 hipError_t set_part_agg_lds_limit(int vk, int lds_bytes) {
-  hipError_t e = hipFuncSetAttribute(part_agg_h_fn(), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  hipError_t e = hipFuncSetAttribute((const void*)part_agg_h_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     lds_bytes);
   if (e != hipSuccess) return e;
   if (const void* f = part_agg_v16_variant(vk)) {
     e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
@@ -1869,13 +1841,12 @@ hipError_t set_part_agg_lds_limit(int vk, int lds_bytes) {
 }
 
 // pv: the V partitions (workgroups [0, pv) of the launch); the H partitions [pv, P) go to their own launch. one_word:
-// the V records are one word (key offset | value id)
+// the V records are one word (key offset | value id): they take the 16-wave variant, unless force_v16 (the passc_v16
+// tuning: 0 / 1, -1 = by the record width) says otherwise
 hipError_t launch_part_agg(int vk, const DevQuery* q, const PartScratch& ps, int P, int pv, bool one_word,
-                           int lds_bytes, hipStream_t s) {
+                           int force_v16, int lds_bytes, hipStream_t s) {
   void* args[] = {(void*)&q, (void*)&ps};
-  const bool v16 = part_agg_v16(one_word) && part_agg_v16_variant(vk) != nullptr;
-  if (!part_agg_h_split() || (pv >= P && !v16))
-    return hipLaunchKernel(part_agg_variant(vk), dim3(P), dim3(kPartAggThreads), args, (size_t)lds_bytes, s);
+  const bool v16 = (force_v16 < 0 ? one_word : force_v16 != 0) && part_agg_v16_variant(vk) != nullptr;
   if (pv > 0) {
     hipError_t e = v16 ? hipLaunchKernel(part_agg_v16_variant(vk), dim3(pv), dim3(kPartAggHThreads), args,
                                          (size_t)lds_bytes, s)
@@ -1883,7 +1854,8 @@ hipError_t launch_part_agg(int vk, const DevQuery* q, const PartScratch& ps, int
     if (e != hipSuccess) return e;
   }
   if (pv >= P) return hipSuccess;
-  return hipLaunchKernel(part_agg_h_fn(), dim3(P - pv), dim3(kPartAggHThreads), args, (size_t)lds_bytes, s);
+  return hipLaunchKernel((const void*)part_agg_h_kernel, dim3(P - pv), dim3(kPartAggHThreads), args, (size_t)lds_bytes,
+                         s);
 }
 
 static int grid_for(int64_t n, int block) {

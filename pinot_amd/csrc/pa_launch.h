@@ -87,7 +87,8 @@ hipError_t launch_limit_passes(const DevQuery* q, const DevSeg* segs, const Limi
                                hipStream_t s);
 // numGroupsLimit walk form: one workgroup per segment with a non-null DevSeg::admit; `words` = bitmap words (K / 32)
 constexpr int64_t kWalkMaxWords = 40000;  // LDS bitmap of at most 160000 bytes
-hipError_t launch_limit_walk(const DevQuery* q, const DevSeg* segs, int nseg, int64_t words, bool mv, hipStream_t s);
+hipError_t launch_limit_walk(const DevQuery* q, const DevSeg* segs, int nseg, int64_t words, bool mv, bool use_tab,
+                             hipStream_t s);
 hipError_t launch_bswap_words(uint32_t* w, int64_t n, hipStream_t s);
 hipError_t launch_hll_lut_numeric(const int64_t* di, const double* dd, int32_t vtype, int32_t card, int32_t log2m,
                                   uint32_t* lut, hipStream_t s);
@@ -101,7 +102,7 @@ hipError_t launch_part_offsets(const DevQuery* hq, const PartScratch& ps, int G,
 // vk: the pass-C variant of the V stream (vk_code / kVkGeneric)
 hipError_t set_part_agg_lds_limit(int vk, int lds_bytes);
 hipError_t launch_part_agg(int vk, const DevQuery* q, const PartScratch& ps, int P, int pv, bool one_word,
-                           int lds_bytes, hipStream_t s);
+                           int force_v16, int lds_bytes, hipStream_t s);
 // Cross-GPU merge of hashed key spaces (pa_merge.hip): a row is every per-key section's elements of one slot
 enum RowOp : int32_t { ROW_ADD_U64 = 0, ROW_ADD_F64 = 1, ROW_MIN_I64 = 2, ROW_MAX_I64 = 3, ROW_MAX_U8 = 4, ROW_KEY = 5 };
 constexpr int kMaxRowSecs = PA_MAX_AGGS + 2;

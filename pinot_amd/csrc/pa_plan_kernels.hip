@@ -313,16 +313,13 @@ bool plan_partitions(pa_query* q, Prep& P, TilePlan& emit_plan, TilePlan& count_
   // Each launch: 4-wave or 16-wave workgroups (the bins are per workgroup: shared by 16 waves they leave LDS for more
   // resident waves when the tile images are small), whichever keeps more waves resident; bins halve (down to 64-byte
   // bursts) while they do not fit or cost resident waves (at least 8 waves per CU hide the per-record gathers).
-  // resident waves per CU the emit plan wants before it keeps larger bins (PA_EMIT_MIN_WAVES: measurement override)
-  static const int emit_min_waves = std::getenv("PA_EMIT_MIN_WAVES") ? std::atoi(std::getenv("PA_EMIT_MIN_WAVES"))
-                                                                      : 2 * kWavesPerWG;
+  // resident waves per CU the emit plan wants before it keeps larger bins
+  constexpr int emit_min_waves = 2 * kWavesPerWG;
   auto plan_emit = [&](int vf, int hh, bool with_v, bool with_h, int& bv, int& bh, int& strat) {
     auto lds_of = [&](int v, int h2) { return emit_state(with_v ? v : 0, with_h ? h2 : 0); };
     TilePlan best;
     int best_bv = bv, best_bh = bh;
-    static const int force_big = std::getenv("PA_EMIT_BIG") ? std::atoi(std::getenv("PA_EMIT_BIG")) : -1;  // (measurement)
     for (int big : {0, 1}) {
-      if (force_big >= 0 && big != force_big) continue;
       const int es = pemit_strat(vf, hh, big, mvc >= 0 ? 1 : 0);
       const int wpw = scan_waves(es);
       int v = bv, h2 = bh;
@@ -744,10 +741,7 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
   h.dma_per_tile = plan.dma;
   h.steps = plan.steps;
   h.debug_stream_only = (s.flags & PA_QF_DEBUG_STREAM_ONLY) ? 1 : 0;
-  {
-    const char* e = std::getenv("PA_DEBUG_EMIT");  // measurement only (see DevQuery::debug_emit)
-    h.debug_emit = e ? std::atoi(e) : 0;
-  }
+  h.debug_emit = q->tune.debug_emit;
   h.lane_major = P.lm ? 1 : 0;
   h.count = (unsigned long long*)q->sections[0].ptr;
   h.matched_docs = (unsigned long long*)q->sections.back().ptr;
@@ -803,10 +797,7 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
       g.ngb = s.num_group_by;
       g.rpl = P.gd_rp_log2;
       g.box = P.gd_box ? 1 : 0;
-      {
-        const char* e = std::getenv("PA_DEBUG_EMIT");  // measurement only (pa_gdense.h knobs; results invalid)
-        g.pad = e ? std::atoi(e) : 0;
-      }
+      g.pad = q->tune.debug_emit;  // (the dense walk's measurement bits, pa_gdense.h)
       for (int j = 0; j < s.num_group_by; ++j) {
         g.gb[j].reg = d.cols[P.gb_slot[j]].lds_off;
         g.gb[j].nbits = d.cols[P.gb_slot[j]].nbits;

@@ -1964,7 +1964,7 @@ __device__ __forceinline__ void part_tile(const DevQuery* __restrict__ q, const 
               w0[k] = ((o_key & kmask) << fsh) | (e == 0 ? first_bit : 0u);
               vi[k] = (int64_t)o_v0 + e;
               von[k] = ok[k] == 2 && !(dbg & 4);
-              alt[k] = ok[k] == 2 ? e : (hmv ? 0u : o_hv);  // (e: measurement only, PA_DEBUG_EMIT bit 2)
+              alt[k] = ok[k] == 2 ? e : (hmv ? 0u : o_hv);  // (e: measurement only, tuning debug_emit bit 2)
             }
             decode_global_batch<kHB>(hwords, vi, von, hnb, id);
 #pragma unroll

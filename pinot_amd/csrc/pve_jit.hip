@@ -57,17 +57,12 @@ constexpr int VC = PVE_VC, KS = PVE_KS, P = PVE_P, BS = PVE_BS, SC = PVE_SC;
 constexpr u32 KR = PVE_KR, KRD = KR ? KR : 1u;
 static_assert(KR <= (1u << KS), "a partition's key offsets fit KS bits");
 constexpr u32 kSentinel = 0xffffffffu;
-#ifndef PVE_PB
 #define PVE_PB 4  // records per lane per put round
-#endif
 #ifndef PVE_ADMIT
 #define PVE_ADMIT 0  // numGroupsLimit walk form: a record is put only when the segment's bitmap admits its key
 #endif
 #ifndef PVE_DBG
-#define PVE_DBG 0  // measurement only (PA_PVE_DBG): 1 = records built but not put, 2 = full bins not stored
-#endif
-#ifndef PVE_DONE_RTN
-#define PVE_DONE_RTN 0  // measurement (PA_PVE_DONE_RTN): the written count's returned value decides a bin is full
+#define PVE_DBG 0  // measurement only (tuning pve_dbg): 1 = records built but not put, 2 = full bins not stored
 #endif
 #ifndef PVE_RW
 #define PVE_RW 1  // words per record: 1 (key offset | value id), 2 (+ a raw 32-bit value), 3 (+ a raw 64-bit value)
@@ -382,13 +377,6 @@ __device__ __forceinline__ void put_round(const Bins& B, bool (&pend)[PB], const
           for (int k = 0; k < RW; ++k) at<l32>(B.bins)[(pp[i] * (u32)BS + s[i]) * (u32)RW + (u32)k] = rr[i][k];
       __atomic_signal_fence(__ATOMIC_SEQ_CST);
       bool full[PB];
-#if PVE_DONE_RTN
-#pragma unroll
-      for (int i = 0; i < PB; ++i)
-        full[i] = s[i] < (u32)BS &&
-                  __hip_atomic_fetch_add(at<l32>(B.done) + pp[i], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ==
-                      (u32)BS - 1u;
-#else
       // written counts without a returned value (no round trip per round): the lane that claimed a bin's last slot
       // waits until every slot of the bin is written (LDS runs each wave's operations in order, so a writer's count
       // follows its record), then flushes it
@@ -410,7 +398,6 @@ __device__ __forceinline__ void put_round(const Bins& B, bool (&pend)[PB], const
                    (u32)BS)
               __builtin_amdgcn_s_sleep(1);
       }
-#endif
       flush_full(B, full, pp, lane);
       bool any = false;
 #pragma unroll

@@ -197,7 +197,8 @@ def _flatten_filter(f, leaves, ops):
 
 class GpuQueryExecutor:
     def __init__(self, query: Q.Query, gpu_segments: List[GpuSegment], flags=0, enforce_num_groups_limit=True,
-                 table_dicts=None, wide_sum_columns=(), value_dicts=None, hash_keys_bound=0, schema=None):
+                 table_dicts=None, wide_sum_columns=(), value_dicts=None, hash_keys_bound=0, schema=None,
+                 tuning=None):
         """table_dicts: optional {group-by column: sorted unique values} — the table-wide dictionary every rank of a
         multi-GPU query must share so that key ids address the same accumulator rows everywhere
         (parallel.table_layout builds it); by default it is the union of these segments' dictionaries.
@@ -210,7 +211,9 @@ class GpuQueryExecutor:
         agrees on the largest rank's bound so every rank's table can take its share of the cross-GPU merge).
         schema: {column: (data type, has dictionary, single value)} agreed across ranks (parallel.table_layout): when
         every segment given here is empty, the executor plans over a one-doc placeholder segment of that schema and never
-        scans it, so the rank still holds a (zero) accumulator block of the agreed layout and joins the cross-GPU merge."""
+        scans it, so the rank still holds a (zero) accumulator block of the agreed layout and joins the cross-GPU merge.
+        tuning: optional {name: int} planner overrides of this query (pa_query_set_tuning; csrc/pa_tuning.h lists them):
+        tests and measurement only."""
         if not gpu_segments:
             raise ValueError("no segments")
         self.table_dicts = table_dicts or {}
@@ -224,6 +227,7 @@ class GpuQueryExecutor:
         self.segs = [g.segment for g in self.gsegs]
         self.device = next((g.device for g in gpu_segments if g.device is not None), None)
         self.flags = flags
+        self.tuning = dict(tuning or {})
         self.enforce_num_groups_limit = enforce_num_groups_limit
         self.handle = None
         self.placeholder = None
@@ -419,6 +423,8 @@ class GpuQueryExecutor:
 
         self.spec = spec
         self.handle = L.check_ptr(lib.pa_query_create(ctypes.byref(spec), len(self.segs)), "pa_query_create")
+        for name, value in self.tuning.items():
+            L.check(lib.pa_query_set_tuning(self.handle, name.encode(), int(value)), "pa_query_set_tuning")
         self._keep = []
         for si, (g, params) in enumerate(zip(self.gsegs, per_seg)):
             arr = (L.LeafParams * max(1, len(params)))()
@@ -522,6 +528,7 @@ class GpuQueryExecutor:
         out["plan"]["count_free_emit"] = int(L.lib().pa_query_count_free_emit(self.handle))
         out["plan"]["partition_keys"] = int(L.lib().pa_query_partition_keys(self.handle))
         out["plan"]["limit_trimming"] = int(L.lib().pa_query_limit_trimming(self.handle))
+        out["plan"]["results_invalid"] = int(L.lib().pa_query_results_invalid(self.handle))
         return out
 
     def fetch_arrays(self, stream=None, pooled=False):

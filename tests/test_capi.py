@@ -36,6 +36,54 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(L.QuerySpec) == 848  # (+ flags2, reserved2)
 
 
+def test_no_stray_environment_reads():
+    """The library's plans and results do not depend on the process environment: every getenv of csrc (the hiprtc kernel
+    sources included) lies in pa_host.h and reads one of the two variables that only log. Overrides are tunings carried
+    by the query (pa_tuning.h, pa_query_set_tuning)."""
+    csrc = os.path.join(ROOT, "pinot_amd", "csrc")
+    seen = []
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".h")):
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        for m in re.finditer(r"getenv", text):
+            assert f == "pa_host.h", (f, text.count("\n", 0, m.start()) + 1)
+            arg = re.match(r'getenv\(\s*"([^"]*)"\s*\)', text[m.start():])
+            assert arg and arg.group(1) in ("PA_DEBUG_PLAN", "PA_JIT_LOG"), text[m.start():m.start() + 60]
+            seen.append(arg.group(1))
+    assert sorted(set(seen)) == ["PA_DEBUG_PLAN", "PA_JIT_LOG"]
+
+
+def test_tuning_calls():
+    """pa_query_set_tuning / pa_query_results_invalid on a query of zero segments (pa_query_create binds nothing and
+    touches no device): a known name with a value in its range is taken; an unknown name and a value outside the range
+    fail with a message; a tuning that skips kernel work marks the results invalid."""
+    from pinot_amd import _lib as L
+    lib = L.lib()
+    spec = L.QuerySpec()
+    spec.num_aggs = 1
+    spec.aggs[0].type = L.PA_AGG_COUNT
+    q = L.check_ptr(lib.pa_query_create(ctypes.byref(spec), 0), "pa_query_create")
+    try:
+        assert lib.pa_query_results_invalid(q) == 0
+        assert lib.pa_query_set_tuning(q, b"gdl_nd", 8) == 0
+        assert lib.pa_query_set_tuning(q, b"gdl_nd", -1) == 0  # (back to the planner's choice)
+        assert lib.pa_query_set_tuning(q, b"no_such_tuning", 1) == -1  # PA_EINVAL
+        assert b"no_such_tuning" in lib.pa_last_error()
+        assert lib.pa_query_set_tuning(q, b"gdl_ring", 5) == -1
+        assert b"gdl_ring" in lib.pa_last_error()
+        assert lib.pa_query_set_tuning(q, b"gdl_dbg", 4) == -1
+        assert lib.pa_query_set_tuning(None, b"gdl_nd", 8) == -1
+        assert lib.pa_query_results_invalid(q) == 0
+        assert lib.pa_query_set_tuning(q, b"gdl_dbg", 1) == 0
+        assert lib.pa_query_results_invalid(q) == 1
+        assert lib.pa_query_set_tuning(q, b"gdl_dbg", 0) == 0
+        assert lib.pa_query_results_invalid(q) == 0
+    finally:
+        lib.pa_query_destroy(q)
+    assert lib.pa_query_results_invalid(None) == -1
+
+
 def test_product_path_does_not_import_oracle():
     """The oracle is a checker only: nothing under pinot_amd/ may import, link or execute it."""
     for dirpath, _, files in os.walk(os.path.join(ROOT, "pinot_amd")):

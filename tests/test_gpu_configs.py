@@ -258,6 +258,29 @@ def test_configs2_high_cardinality_group_by(highcard, variant, count_free):
         assert n <= 2 * 100_000
 
 
+def _tuning_id(t):
+    return "-".join("%s=%d" % kv for kv in t.items())
+
+
+@pytest.mark.parametrize("tuning", [{"pve_nd": 8}, {"pve_bs": 16}, {"pve_q": 1}, {"pve_ring": 3}, {"passc_v16": 0}],
+                         ids=_tuning_id)
+def test_configs2_count_free_emit_tunings(highcard, tuning):
+    """configs[2] untrimmed with one tuning of the count-free V emit or of pass C set away from the planner's choice
+    (8 docs per lane, 16-record bins, the compacted put queue, three tile images per wave, pass C at 8 waves): the
+    count-free emit still runs and the results stay bit-exact."""
+    segs, gs = highcard
+    q = parse_sql("SELECT d1, d2, SUM(m), MIN(m), MAX(m) FROM t GROUP BY d1, d2 LIMIT 2000000 "
+                  "OPTION(numGroupsLimit=2000000)")
+    ex = GpuQueryExecutor(q, gs, tuning=tuning)
+    try:
+        p = _plan(ex)
+        assert p["strategy"] == "partitioned" and p["count_free_emit"] == 1 and p["results_invalid"] == 0, p
+        ex.execute()
+        _compare_arrays(ex, q, segs)
+    finally:
+        ex.close()
+
+
 @pytest.fixture(scope="module")
 def highcard_own():
     segs = [CFG.highcard_own_segment(201 + i, 1_500_000) for i in range(2)]
@@ -348,6 +371,24 @@ def test_configs4_star_query(star, variant, count_free):
     finally:
         ex.close()
     assert n > 250_000 if variant == "untrimmed" else n <= 200_000
+
+
+@pytest.mark.parametrize("tuning", [{"pve_hrun": 0}, {"pve_hb": 2}, {"passc_v16": 1}], ids=_tuning_id)
+def test_configs4_count_free_emit_tunings(star, tuning):
+    """configs[4] untrimmed with one tuning of the count-free H emit or of pass C set away from the planner's choice
+    (one claim per MV value, runs of two values, pass C's V partitions of three-word records at 16 waves): both streams
+    still run count-free and the results stay within the file's bars."""
+    segs, gs = star
+    q = parse_sql("SELECT d1, d2, d3, d4, COUNT(*), SUM(r), DISTINCTCOUNTHLLMV(tags) FROM t GROUP BY d1, d2, d3, d4 "
+                  "LIMIT 1000000 OPTION(numGroupsLimit=1000000)")
+    ex = GpuQueryExecutor(q, gs, tuning=tuning)
+    try:
+        p = _plan(ex)
+        assert p["strategy"] == "partitioned" and p["count_free_emit"] == 2 and p["results_invalid"] == 0, p
+        ex.execute()
+        _compare_arrays(ex, q, segs, rel=DOUBLE_REL)
+    finally:
+        ex.close()
 
 
 def test_configs4_hll_only_keeps_count_pass(star):

@@ -11,8 +11,10 @@ construction. The cases drive each per-segment mechanism of the kernel:
   * SUMs over per-segment arithmetic dictionaries (a dictId offset per segment) and over value tables,
   * a leaf negated in some segments only (an empty range becomes NOT(full range); NOT EQUALS of a value some segments
     lack), and segments a unit clause empties (left out of the kernel's tiles),
-  * packed rows indexed by each segment's local keys, replicated per lane (PA_GDL_RR) and drained at segment switches,
-  * 16 or 8 docs per lane (PA_GDL_ND), drained after every tile (PA_QF_GD_DRAIN_EACH_TILE).
+  * packed rows indexed by each segment's local keys, replicated per lane (tuning gdl_rr) and drained at segment
+    switches,
+  * 16 or 8 docs per lane (tuning gdl_nd), drained after every tile (PA_QF_GD_DRAIN_EACH_TILE).
+The tunings are carried by the query (GpuQueryExecutor(tuning=...), pa_query_set_tuning); the environment steers nothing.
 Bars: bit-exact COUNT, LONG SUM, group keys, numDocsScanned.
 """
 import numpy as np
@@ -91,15 +93,13 @@ QUERIES = (
 @pytest.mark.parametrize("rr", ["64", "1"])
 @pytest.mark.parametrize("nd", ["16", "8"])
 @pytest.mark.parametrize("flags", [0, L.PA_QF_GD_DRAIN_EACH_TILE])
-def test_own_dictionaries_on_the_specialised_kernel(partitions, monkeypatch, nd, flags, rr):
-    """Every QUERIES shape with 16 or 8 docs per lane, the packed rows replicated per lane (as many replicas as fit, up
-    to 64) or not."""
+def test_own_dictionaries_on_the_specialised_kernel(partitions, nd, flags, rr):
+    """Every QUERIES shape with 16 or 8 docs per lane (tuning gdl_nd), the packed rows replicated per lane (tuning
+    gdl_rr: as many replicas as fit, up to 64) or not."""
     segs, gs = partitions
-    monkeypatch.setenv("PA_GDL_ND", nd)
-    monkeypatch.setenv("PA_GDL_RR", rr)
     for sql in QUERIES:
         q = parse_sql(sql)
-        ex = GpuQueryExecutor(q, gs, flags=flags)
+        ex = GpuQueryExecutor(q, gs, flags=flags, tuning={"gdl_nd": int(nd), "gdl_rr": int(rr)})
         try:
             p = ex.stats()["plan"]
             assert p["dense_packed"] == 2 and p["strategy"] == "lds_dense", (sql[:80], p)
@@ -107,6 +107,31 @@ def test_own_dictionaries_on_the_specialised_kernel(partitions, monkeypatch, nd,
         finally:
             ex.close()
         assert_same(got, oracle.run_query(q, segs))
+
+
+def test_work_skipping_tuning_refuses_fetch_and_environment_is_ignored(partitions, monkeypatch):
+    """gdl_dbg=1 (the kernel streams its tiles and returns): the plan reports results_invalid, execute runs, fetch
+    raises. PA_GDL_DBG=1 in the environment, once the same knob, changes nothing: the query matches the oracle."""
+    segs, gs = partitions
+    q = parse_sql(QUERIES[0])
+    ex = GpuQueryExecutor(q, gs, tuning={"gdl_dbg": 1})
+    try:
+        p = ex.stats()["plan"]
+        assert p["results_invalid"] == 1 and p["dense_packed"] == 2, p
+        ex.execute()
+        with pytest.raises(L.PinotAmdError, match="gdl_dbg"):
+            ex.run()
+    finally:
+        ex.close()
+    monkeypatch.setenv("PA_GDL_DBG", "1")
+    ex = GpuQueryExecutor(q, gs)
+    try:
+        p = ex.stats()["plan"]
+        assert p["results_invalid"] == 0 and p["dense_packed"] == 2, p
+        got = ex.run()
+    finally:
+        ex.close()
+    assert_same(got, oracle.run_query(q, segs))
 
 
 def test_own_dictionaries_generic_kernel_agrees(partitions):

@@ -507,11 +507,11 @@ SORTED = 1
 LIMIT_PATHS = [(0, WALK), (L.PA_QF_NO_LIMIT_WALK, SORTED)]
 
 
-def _limit_run(sql, segs, expect_trim=SORTED, rel=0.0, flags=0):
+def _limit_run(sql, segs, expect_trim=SORTED, rel=0.0, flags=0, tuning=None):
     q = parse_sql(sql)
     gsegs = [GpuSegment(sg) for sg in segs]
     try:
-        ex = GpuQueryExecutor(q, gsegs, flags=flags)
+        ex = GpuQueryExecutor(q, gsegs, flags=flags, tuning=tuning)
         try:
             assert ex.stats()["plan"]["limit_trimming"] == int(expect_trim)
             got = ex.run()
@@ -557,12 +557,13 @@ def test_num_groups_limit_walk_every_strategy(flags):
 def test_num_groups_limit_walk_small_key_space(limit):
     """A key space of 120 keys (10 x 12) under a binding limit: nearly every 64-doc replay step of the walk holds the same
     key in several lanes (the replay's first-lane table resolves them; two keys in one table slot fall back to comparing
-    every lane); same first-seen groups as the oracle on both trimming paths."""
+    every lane); same first-seen groups as the oracle on both trimming paths, and on the walk without the table (tuning
+    walk_tab=0: every step compares every lane)."""
     cols = {"k1": ("INT", 10), "k2": ("LONG", 12), "m": ("LONG", 500)}
     segs = [make_segment(760 + i, n, cols) for i, n in enumerate((20000, 3001))]
-    for flags, mode in LIMIT_PATHS:
+    for flags, mode, tuning in [(f, m, None) for f, m in LIMIT_PATHS] + [(0, WALK, {"walk_tab": 0})]:
         got, exp = _limit_run("SELECT k1, k2, COUNT(*), SUM(m) FROM t GROUP BY k1, k2 LIMIT 100000000 "
-                              "OPTION(numGroupsLimit=%d)" % limit, segs, mode, flags=flags)
+                              "OPTION(numGroupsLimit=%d)" % limit, segs, mode, flags=flags, tuning=tuning)
         assert got.num_groups_limit_reached
 
 

@@ -257,7 +257,7 @@ def _bench():
 
 
 def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None, cpu_sample=0, exec_stats=False,
-        warm=0, check=False):
+        warm=0, check=False, tuning=None):
     import torch
     from pinot_amd import parse_sql
     from pinot_amd import _lib as L
@@ -292,7 +292,8 @@ def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None
         def extra_flags(vs_, tag_):
             return dict((t_, f_) for f_, t_ in vs_)[tag_]
         for extra, tag in vs:
-            ex = GpuQueryExecutor(parse_sql(sql), gsegs, flags=flags | extra | (L.PA_QF_NO_FILTER_STATS if exec_stats else 0))
+            ex = GpuQueryExecutor(parse_sql(sql), gsegs, tuning=tuning,
+                                  flags=flags | extra | (L.PA_QF_NO_FILTER_STATS if exec_stats else 0))
             ex.execute(sp)
             for _ in range(warm):  # (untimed: the clocks reach their steady state)
                 ex.scan(sp)
@@ -305,6 +306,12 @@ def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None
             b.record(stream)
             torch.cuda.synchronize()
             ms = a.elapsed_time(b) / reps
+            if ex.stats()["plan"]["results_invalid"]:  # (a tuning that skips kernel work: the scan time is all there is)
+                print(json.dumps({"workload": workload, "plan_name": name + tag, "kernel_ms": round(ms, 4),
+                                  "tuning": tuning, "plan": ex.stats()["plan"], "segments": nseg,
+                                  "docs_per_segment": docs}), flush=True)
+                ex.close()
+                continue
             ex.execute(sp)
             torch.cuda.synchronize()  # fetch_ms = compaction + copies (+ host decode of small blocks) only
             ex.fetch_arrays(sp, pooled=True)  # (first use grows the process's pinned output pool)
@@ -343,7 +350,7 @@ def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None
                 t3 = time.perf_counter()
                 in_f, post = ex.execution_stats(sp, docs_total)
                 plain_ms = (time.perf_counter() - t3) * 1e3
-                fx = GpuQueryExecutor(parse_sql(sql), gsegs, flags=flags | extra_flags(vs, tag))
+                fx = GpuQueryExecutor(parse_sql(sql), gsegs, flags=flags | extra_flags(vs, tag), tuning=tuning)
                 fx.execute(sp)
                 torch.cuda.synchronize()
                 fx.reset(sp)
@@ -393,9 +400,12 @@ def main():
                     help="partitioned aggregation: sweep LDS per partition x workgroups per CU")
     ap.add_argument("--flags", type=int, default=None, help="run this one PA_QF_* flag set only")
     ap.add_argument("--exec-stats", action="store_true", help="also time the execution statistics per plan")
+    ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE",
+                    help="a tuning of every query built (pinot_amd/csrc/pa_tuning.h); repeatable")
     ap.add_argument("--cpu-sample", type=int, default=0,
                     help="keep this many segments on the host: roofline + the C-port CPU baseline per line")
     args = ap.parse_args()
+    tuning = {n: int(v) for n, v in (t.split("=", 1) for t in args.tune)}
     variants = None if args.flags is None else [(args.flags, "_f%d" % args.flags)]
     if args.sweep_part:
         from pinot_amd import _lib as L
@@ -405,7 +415,7 @@ def main():
     torch.cuda.set_device(0)
     for w in (WORKLOADS if args.workload == "all" else [args.workload]):
         run(w, args.segments, args.docs, args.reps, args.plan, args.no_stepmajor, variants, args.cpu_sample,
-            args.exec_stats, args.warm, args.check)
+            args.exec_stats, args.warm, args.check, tuning)
 
 
 if __name__ == "__main__":

@@ -1,9 +1,9 @@
 """Measurement of the query-shape specialised dense kernel (gdl_jit.hip) on bench.py's secondary lines: one segment set
-built once, then every knob setting (environment variables read at query prepare) timed with HIP events around
-back-to-back scans. Settings: default plan; waves / docs per lane / rows shared by two waves (PA_GDL_W, PA_GDL_ND,
-PA_GDL_RS), tile images per wave (PA_GDL_RING); the decomposition stream-only / + filter / + keys and terms without
-the row atomics (PA_GDL_DBG=1 / 2 / 3: results invalid, not checked). Every other
-setting's groups must equal the default plan's.
+built once, then every setting (tunings carried by the query: GpuQueryExecutor(tuning=...)) timed with HIP events around
+back-to-back scans. Settings: default plan; waves / docs per lane / rows shared by two waves (gdl_w, gdl_nd, gdl_rs),
+tile images per wave (gdl_ring); the decomposition stream-only / + filter / + keys and terms without the row atomics
+(gdl_dbg=1 / 2 / 3: results invalid, the library refuses their fetch). Every other setting's groups must equal the
+default plan's.
 
 python tools/gdl_sweep.py [--segments 100] [--docs 10000000] [--own] [--lines sel_10pct,sel_50pct] [--reps 10]
 Prints one JSON line per (line, setting).
@@ -22,27 +22,26 @@ sys.path.insert(0, ROOT)
 
 SETTINGS = [
     ("default", {}),
-    ("stream_only", {"PA_GDL_DBG": "1"}),
-    ("stream_filter", {"PA_GDL_DBG": "2"}),
-    ("w16_nd8_rs2", {"PA_GDL_W": "16", "PA_GDL_ND": "8", "PA_GDL_RS": "2"}),
-    ("w8_nd8", {"PA_GDL_W": "8", "PA_GDL_ND": "8", "PA_GDL_RS": "1"}),
-    ("w8_nd16_rs2", {"PA_GDL_W": "8", "PA_GDL_ND": "16", "PA_GDL_RS": "2"}),
-    ("rr1", {"PA_GDL_RR": "1"}),
-    ("w16_nd8", {"PA_GDL_W": "16", "PA_GDL_ND": "8", "PA_GDL_RS": "1"}),
-    ("walk_no_atomics", {"PA_GDL_DBG": "3"}),
-    ("w12_nd8", {"PA_GDL_W": "12", "PA_GDL_ND": "8", "PA_GDL_RS": "1"}),
-    ("w12_nd16", {"PA_GDL_W": "12", "PA_GDL_ND": "16", "PA_GDL_RS": "1"}),
-    ("w8_nd8_pin", {"PA_GDL_W": "8", "PA_GDL_ND": "8", "PA_GDL_RS": "1"}),
-    ("w16_nd16", {"PA_GDL_W": "16", "PA_GDL_ND": "16", "PA_GDL_RS": "1"}),
-    ("ring3", {"PA_GDL_RING": "3"}),
-    ("ring4", {"PA_GDL_RING": "4"}),
-    ("ring3_w8_nd8", {"PA_GDL_RING": "3", "PA_GDL_W": "8", "PA_GDL_ND": "8"}),
-    ("ring3_w8_nd16", {"PA_GDL_RING": "3", "PA_GDL_W": "8", "PA_GDL_ND": "16"}),
-    ("ring3_w16_nd8", {"PA_GDL_RING": "3", "PA_GDL_W": "16", "PA_GDL_ND": "8"}),
-    ("ring3_rr1", {"PA_GDL_RING": "3", "PA_GDL_RR": "1"}),
+    ("stream_only", {"gdl_dbg": 1}),
+    ("stream_filter", {"gdl_dbg": 2}),
+    ("w16_nd8_rs2", {"gdl_w": 16, "gdl_nd": 8, "gdl_rs": 2}),
+    ("w8_nd8", {"gdl_w": 8, "gdl_nd": 8, "gdl_rs": 1}),
+    ("w8_nd16_rs2", {"gdl_w": 8, "gdl_nd": 16, "gdl_rs": 2}),
+    ("rr1", {"gdl_rr": 1}),
+    ("w16_nd8", {"gdl_w": 16, "gdl_nd": 8, "gdl_rs": 1}),
+    ("walk_no_atomics", {"gdl_dbg": 3}),
+    ("w12_nd8", {"gdl_w": 12, "gdl_nd": 8, "gdl_rs": 1}),
+    ("w12_nd16", {"gdl_w": 12, "gdl_nd": 16, "gdl_rs": 1}),
+    ("w8_nd8_pin", {"gdl_w": 8, "gdl_nd": 8, "gdl_rs": 1}),
+    ("w16_nd16", {"gdl_w": 16, "gdl_nd": 16, "gdl_rs": 1}),
+    ("ring3", {"gdl_ring": 3}),
+    ("ring4", {"gdl_ring": 4}),
+    ("ring3_w8_nd8", {"gdl_ring": 3, "gdl_w": 8, "gdl_nd": 8}),
+    ("ring3_w8_nd16", {"gdl_ring": 3, "gdl_w": 8, "gdl_nd": 16}),
+    ("ring3_w16_nd8", {"gdl_ring": 3, "gdl_w": 16, "gdl_nd": 8}),
+    ("ring3_rr1", {"gdl_ring": 3, "gdl_rr": 1}),
     ("default_b", {}),
 ]
-KNOBS = ("PA_GDL_W", "PA_GDL_ND", "PA_GDL_RS", "PA_GDL_DBG", "PA_GDL_RR", "PA_GDL_RING")
 
 
 def main():
@@ -81,12 +80,9 @@ def main():
     sp = stream.cuda_stream
     for name, n_ids in lines:
         sql = B.secondary_query_own(n_ids, args.segments) if args.own else B.secondary_query(n_ids)
-        ref = None
-        for sname, env in settings:
-            for k in KNOBS:
-                os.environ.pop(k, None)
-            os.environ.update(env)
-            ex = GpuQueryExecutor(parse_sql(sql), gsegs)
+        ref, matched = None, 0
+        for sname, tuning in settings:
+            ex = GpuQueryExecutor(parse_sql(sql), gsegs, tuning=tuning)
             try:
                 plan = ex.stats()["plan"]
                 ex.execute(sp)
@@ -101,24 +97,22 @@ def main():
                 b.record(stream)
                 torch.cuda.synchronize()
                 ms = a.elapsed_time(b) / args.reps
-                ex.execute(sp)
-                keys, counts, outs = ex.fetch_arrays(sp)
-                matched = int(L.lib().pa_query_matched_docs(ex.handle))
-                algo = B.algorithmic_bytes(ex, matched)
                 same = None
-                if "PA_GDL_DBG" not in env:
+                if not plan["results_invalid"]:  # (else: the matched docs of the last checked setting)
+                    ex.execute(sp)
+                    keys, counts, outs = ex.fetch_arrays(sp)
+                    matched = int(L.lib().pa_query_matched_docs(ex.handle))
                     cur = (keys.tolist(), counts.tolist(), [o.tolist() for o in outs])
                     ref = cur if ref is None else ref
                     same = cur == ref
+                algo = B.algorithmic_bytes(ex, matched)
             finally:
                 ex.close()
-            print(json.dumps({"line": name, "own_dictionaries": args.own, "setting": sname, "env": env,
+            print(json.dumps({"line": name, "own_dictionaries": args.own, "setting": sname, "tuning": tuning,
                               "kernel_ms": round(ms, 4), "frac": round(algo / (ms * 1e-3) / 8e12, 4),
                               "algorithmic_bytes": algo, "dense_packed": plan["dense_packed"],
                               "variant": plan["variant"], "lds_bytes": plan["lds_bytes"], "same_groups": same}),
                   flush=True)
-    for k in KNOBS:
-        os.environ.pop(k, None)
     for g in gsegs:
         g.close()
 
