@@ -35,6 +35,11 @@
  *      and the in-server merge of those partial results
  *        operator/combine/AggregationCombineOperator.java, GroupByCombineOperator.java:110
  *      (segments of one GPU accumulate into ONE table-wide key space, so no per-segment merge is needed).
+ *  pa_query_fetch_histogram / pa_query_percentiles (PA_AGG_VALUE_HISTOGRAM)
+ *      replace aggregation/function/PercentileAggregationFunction.java and PercentileMVAggregationFunction.java:
+ *      aggregate / aggregateGroupBySV / aggregateGroupByMV (every value into a DoubleArrayList) become per-group value
+ *      histograms inside the scan, extractAggregationResult / extractGroupByResult the compacted (value id, count)
+ *      pairs, extractFinalResult (sort + index at the percentile's rank) a rank select over the bins on the GPU.
  *  pa_query_accumulators / layout
  *      exposes the device accumulators so the cross-GPU merge of partial aggregates runs as an RCCL
  *      reduce (SUM for COUNT/SUM, MIN, MAX, MAX for HLL registers) — the multi-GPU analogue of
@@ -102,6 +107,16 @@ extern "C" {
                                   table-wide value id of the column (pa_agg_spec.num_values of them; segment dictIds are
                                   mapped by pa_query_bind_value_remap) — the value set of DistinctCountAggregationFunction
                                   (BaseDistinctAggregateAggregationFunction) as a bitmap over the table's values */
+#define PA_AGG_VALUE_HISTOGRAM 7 /* per group, how many times each value of a dictionary-encoded column was aggregated:
+                                    one 64-bit count per table-wide value id (pa_agg_spec.num_values of them, segment
+                                    dictIds mapped by pa_query_bind_value_remap, both as for DISTINCTCOUNT). The bins in
+                                    ascending value order are PercentileAggregationFunction's DoubleArrayList as a multiset
+                                    (aggregate / aggregateGroupBySV add every value; merge is addAll = bin-wise addition);
+                                    over a multi-value column every value of the doc counts
+                                    (PercentileMVAggregationFunction). Direct key spaces only: pa_query_prepare fails with
+                                    PA_EUNSUPPORTED over a hashed key space, and for a raw or STRING / BYTES column. Read
+                                    with pa_query_fetch_histogram / pa_query_percentiles; pa_query_fetch writes nothing
+                                    for it */
 /* SUM / MIN / MAX / DISTINCTCOUNTHLL over a multi-value column aggregate every value of the doc (SUMMV, MINMV, MAXMV,
  * DISTINCTCOUNTHLLMV); a multi-value group-by column expands a doc into one key per value (cartesian product over
  * several MV columns), as DictionaryBasedGroupKeyGenerator.getIntRawKeys does. */
@@ -156,7 +171,8 @@ typedef struct {
   int32_t column_id; /* ignored for COUNT */
   int32_t log2m;     /* DISTINCTCOUNTHLL only (CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M = 8) */
   int32_t flags;     /* PA_AGGF_* */
-  int64_t num_values; /* DISTINCTCOUNT: size of the column's table-wide value dictionary (ignored otherwise) */
+  int64_t num_values; /* DISTINCTCOUNT / VALUE_HISTOGRAM: size of the column's table-wide value dictionary (ignored
+                         otherwise) */
 } pa_agg_spec;
 
 /* SUM over an INT/LONG column: keep the exact 96-bit (low 32 unsigned, high 32 signed) pair accumulator
@@ -254,7 +270,7 @@ pa_query* pa_query_create(const pa_query_spec* spec, int32_t num_segments);
 int pa_query_bind_segment(pa_query* q, int32_t index, const pa_segment* seg,
                           const pa_leaf_params* leaf_params, const int32_t* const* group_remaps);
 
-/* DISTINCTCOUNT aggregation `agg` on the segment bound at `index`: remap[d] = the table-wide value id of the segment's
+/* DISTINCTCOUNT or VALUE_HISTOGRAM aggregation `agg` on the segment bound at `index`: remap[d] = the table-wide value id of the segment's
  * dictId d (int32[segment cardinality]; NULL = identity, the segment's dictionary IS the table-wide one). Call after
  * pa_query_bind_segment, before pa_query_prepare. */
 int pa_query_bind_value_remap(pa_query* q, int32_t index, int32_t agg, const int32_t* remap);
@@ -296,6 +312,9 @@ int pa_query_scan(pa_query* q, void* stream);
                               reducible across GPUs (slots differ): merge fetched groups by key instead */
 #define PA_ACC_PRESENCE_U8 9 /* reduce MAX; DISTINCTCOUNT: [key * stride + value id] = 1 if the group saw the value,
                                 stride = num_values rounded up to 16 bytes */
+#define PA_ACC_HIST_U64 10 /* reduce SUM; VALUE_HISTOGRAM: [key * stride + value id] = times the group aggregated the
+                              value, stride = num_values rounded up to a multiple of 2 (whole 16-byte units; a padding
+                              bin stays 0). 64 bits: a GPU holds tens of billions of docs, so one bin can pass 2^32 */
 /* All sections live in one device block of pa_query_accumulator_bytes() bytes (256-byte aligned sections).
  * pa_query_set_accumulator_buffer lets the caller own that block (e.g. memory its collective library
  * registered) instead of the library: call after pa_query_prepare; `bytes` must be >= the size. */
@@ -307,13 +326,38 @@ void* pa_query_section(const pa_query* q, int32_t section, int32_t* kind, int64_
 
 /* Compacts the non-empty keys (count > 0) in ascending key order and copies them to the host.
  * out_keys: int64[capacity]; out_counts: int64[capacity]; out_aggs[i]: double[capacity] for
- * COUNT/SUM/MIN/MAX (the reference's intermediate type), uint8[capacity << log2m] for HLL registers.
+ * COUNT/SUM/MIN/MAX (the reference's intermediate type), uint8[capacity << log2m] for HLL registers. Nothing is
+ * written for a VALUE_HISTOGRAM aggregation (0 bytes per group: its out_aggs[i] may be NULL); its bins are read with
+ * pa_query_fetch_histogram / pa_query_percentiles.
  * For aggregation-only queries key 0 is always returned (count may be 0).
  * Returns the number of groups (may exceed capacity: then only `capacity` were written), <0 on error.
  * capacity = 0 (output pointers may be NULL) only counts the groups — for large key spaces just the GPU count pass —
  * so a caller can size its arrays exactly before the real fetch. Synchronises `stream`. */
 int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out_keys,
                        int64_t* out_counts, void* const* out_aggs);
+
+/* The bins of VALUE_HISTOGRAM aggregation `agg` for the groups pa_query_fetch returns for the current accumulators, in
+ * the same order (num_groups = that call's result): per group the non-zero bins in ascending table-wide value id, as
+ * (value id, count) pairs. out_row_ends[g] (int64[num_groups]) = end offset of group g's pairs (its start is
+ * out_row_ends[g - 1], 0 for g = 0); out_value_ids (int32[capacity]) / out_value_counts (int64[capacity]) hold the pairs.
+ * Returns the total number of pairs (may exceed capacity: then only the first `capacity` pairs were written), <0 on
+ * error. capacity = 0 only counts (the two pair arrays may be NULL). This is the intermediate result of
+ * PercentileAggregationFunction.extractAggregationResult / extractGroupByResult (the DoubleArrayList of every value, as
+ * value -> multiplicity) and of PercentileMVAggregationFunction; the non-zero count, scan and compaction run on the GPU
+ * (pa_hist.hip), then one copy per output array. Synchronises `stream`. */
+int64_t pa_query_fetch_histogram(pa_query* q, void* stream, int32_t agg, int64_t num_groups, int64_t capacity,
+                                 int64_t* out_row_ends, int32_t* out_value_ids, int64_t* out_value_counts);
+
+/* Final results of VALUE_HISTOGRAM aggregation `agg` for the same groups, without moving the bins: out_value_ids
+ * [g * num_percentiles + j] = the table-wide value id at the rank of percentiles[j] (0..100, else PA_EINVAL; at most
+ * PA_MAX_PERCENTILES) in group g, or -1 for a group whose bins are all zero. Replaces
+ * PercentileAggregationFunction.extractFinalResult (sort, then values[(int) ((long) size * percentile / 100)], or
+ * values[size - 1] at 100): rank = total - 1 when p == 100, else (int64_t)((double)total * p / 100); the result is the
+ * first bin whose inclusive prefix sum exceeds the rank (a rank select over the ascending bins, pa_hist.hip).
+ * Synchronises `stream`. */
+#define PA_MAX_PERCENTILES 64
+int pa_query_percentiles(pa_query* q, void* stream, int32_t agg, int64_t num_groups, int32_t num_percentiles,
+                         const double* percentiles, int32_t* out_value_ids);
 
 /* numDocsScanned captured by the last pa_query_fetch (docs that passed the filter; with a multi-value group-by this
  * differs from the sum of the group counts), <0 on error. */

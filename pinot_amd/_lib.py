@@ -16,7 +16,8 @@ PA_MAX_AGGS = 16
 PA_INT, PA_LONG, PA_FLOAT, PA_DOUBLE, PA_STRING, PA_BYTES = range(6)
 PA_LEAF_DICT_RANGE, PA_LEAF_DICT_SET, PA_LEAF_RAW_RANGE, PA_LEAF_MV_DICT_RANGE, PA_LEAF_MV_DICT_SET, PA_LEAF_RAW_SET = range(6)
 PA_OP_LEAF, PA_OP_AND, PA_OP_OR, PA_OP_NOT = range(4)
-PA_AGG_COUNT, PA_AGG_SUM, PA_AGG_MIN, PA_AGG_MAX, PA_AGG_DISTINCTCOUNTHLL, PA_AGG_COUNT_MV, PA_AGG_DISTINCTCOUNT = range(7)
+PA_AGG_COUNT, PA_AGG_SUM, PA_AGG_MIN, PA_AGG_MAX, PA_AGG_DISTINCTCOUNTHLL, PA_AGG_COUNT_MV, PA_AGG_DISTINCTCOUNT, \
+    PA_AGG_VALUE_HISTOGRAM = range(8)
 PA_QF_STAGE_ALL = 1
 PA_QF_FORCE_GLOBAL = 2
 PA_QF_STEPS16 = 1 << 4
@@ -49,7 +50,8 @@ PA_STATS_NON_SCAN, PA_STATS_HOST = -1, -2
 PA_BIT_AND, PA_BIT_OR, PA_BIT_NOT = -1, -2, -3
 PA_BIT_PROG_MAX = 64
 PA_ACC_COUNT_U64, PA_ACC_SUM_I64, PA_ACC_SUM_F64, PA_ACC_MIN_I64, PA_ACC_MAX_I64, PA_ACC_HLL_U8, \
-    PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8 = range(10)
+    PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64 = range(11)
+PA_MAX_PERCENTILES = 64
 ABI_VERSION = 5
 
 # every symbol declared in include/pinot_amd.h
@@ -62,7 +64,7 @@ EXPORTED = [
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_partition_keys",
     "pa_query_accumulator_bytes", "pa_query_set_accumulator_buffer", "pa_query_num_sections", "pa_query_section",
-    "pa_query_fetch", "pa_query_matched_docs", "pa_query_key_layout", "pa_query_limit_trimming",
+    "pa_query_fetch", "pa_query_fetch_histogram", "pa_query_percentiles", "pa_query_matched_docs", "pa_query_key_layout", "pa_query_limit_trimming",
     "pa_query_num_groups_limit_reached", "pa_query_stats", "pa_query_leaf_bitmap_words", "pa_query_leaf_bitmaps",
     "pa_bitmap_counts_scratch_bytes", "pa_bitmap_counts", "pa_query_filter_counts",
     "pa_query_plan", "pa_query_column_staged", "pa_query_leap_leaf", "pa_query_leap_counts",
@@ -155,6 +157,8 @@ def _declare(lib):
         "pa_query_num_sections": (i32, [vp]),
         "pa_query_section": (vp, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64)]),
         "pa_query_fetch": (i64, [vp, vp, i64, vp, vp, vp]),
+        "pa_query_fetch_histogram": (i64, [vp, vp, i32, i64, i64, vp, vp, vp]),
+        "pa_query_percentiles": (ctypes.c_int, [vp, vp, i32, i64, i32, vp, vp]),
         "pa_query_matched_docs": (i64, [vp]),
         "pa_query_key_layout": (ctypes.c_int, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "pa_query_limit_trimming": (i32, [vp]),

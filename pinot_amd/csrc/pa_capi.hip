@@ -95,7 +95,8 @@ int pa_query_bind_value_remap(pa_query* q, int32_t index, int32_t agg, const int
   if (q->prepared) return fail(PA_EINVAL, "query already prepared");
   if (!q->segs[index]) return fail(PA_EINVAL, "bind the segment before its value remaps");
   const pa_agg_spec& A = q->spec.aggs[agg];
-  if (A.type != PA_AGG_DISTINCTCOUNT) return fail(PA_EINVAL, "value remaps belong to DISTINCTCOUNT aggregations");
+  if (!value_id_agg(A.type))
+    return fail(PA_EINVAL, "value remaps belong to DISTINCTCOUNT and VALUE_HISTOGRAM aggregations");
   auto it = q->segs[index]->cols.find(A.column_id);
   if (it == q->segs[index]->cols.end()) return fail(PA_EINVAL, "aggregation column missing in segment");
   q->vremaps[index][agg].clear();

@@ -207,7 +207,8 @@ struct DevAgg {
   int64_t* acc_i64;          // SUM(int) [K], SUM(long) [2K: lo, hi], MIN / MAX (ordered encoding for doubles)
   double* acc_f64;           // SUM(double)
   uint8_t* acc_hll;          // [num_keys << log2m] one byte per register; DISTINCTCOUNT: [num_keys * nvals] presence
-  int64_t nvals;             // DISTINCTCOUNT: presence bytes per key (table-wide values, rounded up to 16)
+  int64_t nvals;             // DISTINCTCOUNT: presence bytes per key (table-wide values, rounded up to 16);
+                             // VALUE_HISTOGRAM: bins per key (table-wide values, rounded up to 2), u64 in acc_i64
   int32_t lds_off;           // LDS strategy / partition aggregation: byte offset of the WG-private copy
   int32_t pay_off;           // partitioned aggregation, V_FMT_GEN: word offset of the value inside a V record
   // STRAT_LANE_DICT, SUM over a dictionary column that every bound segment shares: per-workgroup dictId counts in LDS

@@ -41,6 +41,7 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
         for (int a = 0; a < s.num_aggs; ++a) {
           if (!out_aggs || !out_aggs[a]) continue;
           const pa_agg_spec& A = s.aggs[a];
+          if (A.type == PA_AGG_VALUE_HISTOGRAM) continue;  // 0 bytes per row: pa_query_fetch_histogram reads the bins
           double* outd = (double*)out_aggs[a];
           if (A.type == PA_AGG_COUNT) {
             outd[n] = (double)hc[r];
@@ -142,7 +143,8 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
       f.src[a] = q->hq.aggs[a].src;
       f.sec[a] = q->agg_section[a] >= 0 ? q->sections[q->agg_section[a]].ptr : nullptr;
       f.per[a] = A.type == PA_AGG_DISTINCTCOUNT ? presence_stride(A)
-                                                : (A.type == PA_AGG_DISTINCTCOUNTHLL ? (int64_t(1) << A.log2m) : 8);
+                 : A.type == PA_AGG_VALUE_HISTOGRAM ? 0  // (nothing staged or copied)
+                 : (A.type == PA_AGG_DISTINCTCOUNTHLL ? (int64_t(1) << A.log2m) : 8);
       off[a] = bytes;
       bytes += ((size_t)rows_cap * (size_t)f.per[a] + 255) & ~(size_t)255;
     }
@@ -160,7 +162,7 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
     if (out_keys) PA_HIP(hipMemcpyAsync(out_keys, f.keys, (size_t)rows_cap * 8, hipMemcpyDeviceToHost, st));
     if (out_counts) PA_HIP(hipMemcpyAsync(out_counts, f.counts, (size_t)rows_cap * 8, hipMemcpyDeviceToHost, st));
     for (int a = 0; a < s.num_aggs; ++a)
-      if (out_aggs && out_aggs[a])
+      if (out_aggs && out_aggs[a] && f.per[a] > 0)
         PA_HIP(hipMemcpyAsync(out_aggs[a], f.out[a], (size_t)rows_cap * (size_t)f.per[a], hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
     return m;
@@ -170,7 +172,7 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
   std::memset(&d, 0, sizeof(d));
   std::vector<int> secs = {0};
   for (int a = 0; a < s.num_aggs; ++a)
-    if (q->agg_section[a] >= 0) secs.push_back(q->agg_section[a]);
+    if (q->agg_section[a] >= 0 && s.aggs[a].type != PA_AGG_VALUE_HISTOGRAM) secs.push_back(q->agg_section[a]);
   if (q->hashed) secs.push_back(q->keys_section);
   // hashed key spaces: every non-empty slot is needed to sort by packed key before the capacity cut
   const int64_t rows_needed = q->hashed ? m : std::min<int64_t>(m, std::max<int64_t>(capacity, 0));

@@ -189,6 +189,10 @@ inline int arena_grow(ScratchArena* a, size_t bytes) {
 
 // DISTINCTCOUNT presence bytes per key: the table-wide value count rounded up to whole 16-byte units
 inline int64_t presence_stride(const pa_agg_spec& A) { return (A.num_values + 15) & ~int64_t(15); }
+// VALUE_HISTOGRAM bins per key: the table-wide value count rounded up to whole 16-byte units of 8-byte bins
+inline int64_t hist_stride(const pa_agg_spec& A) { return (A.num_values + 1) & ~int64_t(1); }
+// DISTINCTCOUNT and VALUE_HISTOGRAM index their accumulators by the column's table-wide value id
+inline bool value_id_agg(int32_t type) { return type == PA_AGG_DISTINCTCOUNT || type == PA_AGG_VALUE_HISTOGRAM; }
 // element bytes of an accumulator section
 inline size_t section_es(int32_t kind) { return (kind == PA_ACC_HLL_U8 || kind == PA_ACC_PRESENCE_U8) ? 1 : 8; }
 
@@ -284,6 +288,9 @@ struct pa_query {
   int limit_grid = 0;
   DevBuf lim_keys, lim_pos, lim_hist, lim_sel, lim_thresh;
   DevBuf stat_buf;  // pa_query_filter_counts: leaf bitmaps, scratch, counts, jobs (grown on demand)
+  // pa_query_fetch_histogram / pa_query_percentiles (pa_hist.hip, grown on demand): the fetched groups' keys with their
+  // row offsets or percentile results; the compacted (value id, count) pairs
+  DevBuf hist_buf, hist_pairs;
   DevBuf merge_buf;  // pa_query_pack_rows / pa_query_merge_rows: row -> slot map and counters (grown on demand)
   DevBuf leap_buf;  // fused statistics (default; PA_QF_NO_FILTER_STATS turns them off): per segment (matched docs, leaps, gave up)
   int leap_leaf = -1;  // the eager leaf (spec order) when the scan counts the leaps
@@ -314,6 +321,8 @@ struct pa_query {
     dev_free(stat_buf);
     dev_free(leap_buf);
     dev_free(merge_buf);
+    dev_free(hist_buf);
+    dev_free(hist_pairs);
     dev_free(lim_admit);
     dev_free(dgdplans);
     dev_free(jit_args);

@@ -200,7 +200,7 @@ int plan_slots(pa_query* q, Prep& P) {
   P.agg_slot.assign(s.num_aggs, 0);
   for (int a = 0; a < s.num_aggs; ++a) {
     const int t = s.aggs[a].type;
-    if (t < PA_AGG_COUNT || t > PA_AGG_DISTINCTCOUNT) return fail(PA_EINVAL, "bad aggregation type");
+    if (t < PA_AGG_COUNT || t > PA_AGG_VALUE_HISTOGRAM) return fail(PA_EINVAL, "bad aggregation type");
     if (t == PA_AGG_COUNT) continue;
     P.agg_slot[a] = slot_of(q, s.aggs[a].column_id);
     if (P.agg_slot[a] < 0) return fail(PA_EUNSUPPORTED, "too many distinct columns in one query");
@@ -208,6 +208,8 @@ int plan_slots(pa_query* q, Prep& P) {
       return fail(PA_EINVAL, "log2m must be 4..16");
     if (t == PA_AGG_DISTINCTCOUNT && (s.aggs[a].num_values < 1 || s.aggs[a].num_values > INT32_MAX))
       return fail(PA_EINVAL, "DISTINCTCOUNT needs the table-wide value count (1..2^31-1)");
+    if (t == PA_AGG_VALUE_HISTOGRAM && (s.aggs[a].num_values < 1 || s.aggs[a].num_values > INT32_MAX))
+      return fail(PA_EINVAL, "VALUE_HISTOGRAM needs the table-wide value count (1..2^31-1)");
   }
   // Post-filter columns (group-by keys, aggregated values) are staged with the filter columns when the filter lets
   // enough docs per wave tile through; below that each surviving doc reads them from HBM. Staging costs the columns'
@@ -907,9 +909,13 @@ int build_segments(pa_query* q, Prep& P) {
         P.agg_src[a] = SRC_INT;
         continue;
       }
-      if (A.type == PA_AGG_DISTINCTCOUNT) {
+      if (value_id_agg(A.type)) {
+        const bool hist = A.type == PA_AGG_VALUE_HISTOGRAM;
         if (c->kind != COL_SV_DICT && c->kind != COL_MV_DICT)
-          return fail(PA_EUNSUPPORTED, "DISTINCTCOUNT needs a dictionary-encoded column");
+          return fail(PA_EUNSUPPORTED, hist ? "VALUE_HISTOGRAM needs a dictionary-encoded column"
+                                            : "DISTINCTCOUNT needs a dictionary-encoded column");
+        if (hist && (c->vtype == PA_STRING || c->vtype == PA_BYTES))
+          return fail(PA_EUNSUPPORTED, "VALUE_HISTOGRAM needs a numeric column (percentiles of STRING / BYTES values)");
         const std::vector<int32_t>& rm = q->vremaps[si][a];
         if (!rm.empty()) {
           void* dp = nullptr;
@@ -917,7 +923,7 @@ int build_segments(pa_query* q, Prep& P) {
           if (rc) return rc;
           d.hll_lut[a] = (const uint32_t*)dp;
         } else if (c->cardinality > A.num_values) {
-          return fail(PA_EINVAL, "segment dictionary larger than the DISTINCTCOUNT value space without a remap");
+          return fail(PA_EINVAL, "segment dictionary larger than the aggregation's value space without a remap");
         }
         P.agg_src[a] = SRC_INT;
         P.val_fast[a] = 0;
@@ -982,6 +988,14 @@ int plan_accumulators(pa_query* q, Prep& P) {
       case PA_AGG_DISTINCTCOUNTHLL: sec.push_back({PA_ACC_HLL_U8, K << A.log2m}); break;
       case PA_AGG_COUNT_MV: sec.push_back({PA_ACC_SUM_I64, K}); break;
       case PA_AGG_DISTINCTCOUNT: sec.push_back({PA_ACC_PRESENCE_U8, K * presence_stride(A)}); break;
+      case PA_AGG_VALUE_HISTOGRAM:
+        // (a hashed slot table has no row a key owns before the scan, and its rows would be 2 x the key bound long)
+        if (q->hashed)
+          return fail(PA_EUNSUPPORTED, "VALUE_HISTOGRAM over a hashed key space (a raw group-by column, or a product of "
+                                       "group-by cardinalities too large to address directly) is not supported");
+        if (K > INT64_MAX / 8 / hist_stride(A)) return fail(PA_ENOMEM, "VALUE_HISTOGRAM: keys x values too large");
+        sec.push_back({PA_ACC_HIST_U64, K * hist_stride(A)});
+        break;
     }
     q->agg_section[a] = (int)sec.size() - 1;
   }
@@ -1011,6 +1025,7 @@ int plan_accumulators(pa_query* q, Prep& P) {
     P.agg_lds[a] = P.lds_acc;
     const size_t bytes = A.type == PA_AGG_DISTINCTCOUNTHLL ? ((size_t)K << A.log2m) * 4
                          : A.type == PA_AGG_DISTINCTCOUNT ? (size_t)K * presence_stride(A)
+                         : A.type == PA_AGG_VALUE_HISTOGRAM ? (size_t)K * hist_stride(A) * 4  // WG-private u32 bins
                          : (size_t)K * 8 * ((A.type == PA_AGG_SUM && P.agg_src[a] == SRC_LONG) ? 2 : 1);
     P.lds_acc += (bytes + 15) & ~(size_t)15;
   }

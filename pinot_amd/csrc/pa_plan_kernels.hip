@@ -181,7 +181,7 @@ bool plan_partitions(pa_query* q, Prep& P, TilePlan& emit_plan, TilePlan& count_
   for (int a = 0; a < s.num_aggs; ++a) {
     const int t = s.aggs[a].type;
     if (t == PA_AGG_COUNT) continue;
-    if (t == PA_AGG_COUNT_MV || t == PA_AGG_DISTINCTCOUNT) { PLAN_LOG("partitioned: no (exit 1)"); return false; }
+    if (t == PA_AGG_COUNT_MV || value_id_agg(t)) { PLAN_LOG("partitioned: no (exit 1)"); return false; }
     if (t == PA_AGG_DISTINCTCOUNTHLL) {
       if (hll >= 0) { PLAN_LOG("partitioned: no (exit 2)"); return false; }  // one H stream per query
       hll = a;
@@ -655,7 +655,19 @@ int plan_kernels(pa_query* q, Prep& P, TilePlan& plan, TilePlan& count_plan) {
       P.lds_acc = lane_b;
     }
   }
-  if (q->strategy == STRAT_GLOBAL && !(s.flags & PA_QF_FORCE_GLOBAL) && !q->limit_mode && !q->hashed &&
+  // VALUE_HISTOGRAM: the LDS strategy's workgroup-private bins are 32 bits wide, so they can be trusted only while no
+  // bin can reach 2^32: the bound segments' docs (for a multi-value column, its values) must total less than that
+  bool hist_lds_ok = true;
+  for (int a = 0; a < s.num_aggs; ++a) {
+    if (s.aggs[a].type != PA_AGG_VALUE_HISTOGRAM) continue;
+    uint64_t adds = 0;
+    for (const pa_segment* seg : q->segs) {
+      const Column* c = seg->cols.at(s.aggs[a].column_id);
+      adds += c->kind == COL_MV_DICT ? (uint64_t)c->total_values : (uint64_t)seg->num_docs;
+    }
+    hist_lds_ok = hist_lds_ok && adds < (uint64_t(1) << 32);
+  }
+  if (q->strategy == STRAT_GLOBAL && !(s.flags & PA_QF_FORCE_GLOBAL) && !q->limit_mode && !q->hashed && hist_lds_ok &&
       P.lds_acc <= 64 * 1024 && (P.dense || (s.flags & PA_QF_FORCE_LDS))) {
     plan = plan_pick(STRAT_LDS, P.lds_acc);
     if (plan.score >= 0) q->strategy = STRAT_LDS;
@@ -909,7 +921,8 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
     A.slot = P.agg_slot[a];
     A.log2m = s.aggs[a].log2m;
     A.src = P.agg_src[a];
-    A.nvals = s.aggs[a].type == PA_AGG_DISTINCTCOUNT ? presence_stride(s.aggs[a]) : 0;
+    A.nvals = s.aggs[a].type == PA_AGG_DISTINCTCOUNT ? presence_stride(s.aggs[a])
+              : s.aggs[a].type == PA_AGG_VALUE_HISTOGRAM ? hist_stride(s.aggs[a]) : 0;
     if (is_gdense(q->strategy)) {
       A.gd_vs = P.gd_vs[a];
       A.gd_op = P.gd_op[a];

@@ -192,7 +192,7 @@ __device__ __forceinline__ AggValue agg_value(const DevAgg& A, int a, const DevS
     const uint32_t id = decode_dict_id<G>(c, img, doc_local, doc);
     if (A.type == PA_AGG_DISTINCTCOUNTHLL) {
       out.i = gp(seg->hll_lut[a])[id];
-    } else if (A.type == PA_AGG_DISTINCTCOUNT) {
+    } else if (A.type == PA_AGG_DISTINCTCOUNT || A.type == PA_AGG_VALUE_HISTOGRAM) {
       out.i = seg->hll_lut[a] != nullptr ? gp(seg->hll_lut[a])[id] : id;  // table-wide value id
     } else if (A.src != SRC_DOUBLE) {
       out.i = gp(c.dict_i64)[id];
@@ -265,6 +265,12 @@ struct Acc {
   __device__ __forceinline__ void set_presence(const DevAgg& A, int64_t key, int64_t v) const {
     if (STRAT == STRAT_LDS) ((uint8_t*)(lds + A.lds_off))[key * A.nvals + v] = 1;
     else gp(A.acc_hll)[key * A.nvals + v] = 1;
+  }
+  // VALUE_HISTOGRAM: the group aggregated value id v once more (LDS: workgroup-private u32 bins, flushed as u64 adds;
+  // the planner picks LDS only when no bin can reach 2^32)
+  __device__ __forceinline__ void add_hist(const DevAgg& A, int64_t key, int64_t v) const {
+    if (STRAT == STRAT_LDS) atomicAdd((uint32_t*)(lds + A.lds_off) + key * A.nvals + v, 1u);
+    else __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + key * A.nvals + v, 1ull, RLX);
   }
   __device__ __forceinline__ void max_hll(const DevAgg& A, int64_t key, uint32_t jr) const {
     const int64_t idx = (key << A.log2m) + (jr >> 8);
@@ -353,6 +359,8 @@ __device__ __forceinline__ void accumulate_step(const DevQuery* __restrict__ q, 
         if (in) acc.max_hll(A, key, (uint32_t)v.i);
       } else if (A.type == PA_AGG_DISTINCTCOUNT) {
         if (in) acc.set_presence(A, key, v.i);
+      } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
+        if (in) acc.add_hist(A, key, v.i);
       } else if (grouped) {
         if (A.type == PA_AGG_SUM) {
           if (A.src == SRC_INT) {
@@ -405,7 +413,8 @@ __device__ __forceinline__ AggValue agg_value_mv(const DevAgg& A, int a, const D
   AggValue out{0, 0.0};
   const uint32_t id = decode_global(c.words, vi, c.nbits);
   if (A.type == PA_AGG_DISTINCTCOUNTHLL) out.i = gp(seg->hll_lut[a])[id];
-  else if (A.type == PA_AGG_DISTINCTCOUNT) out.i = seg->hll_lut[a] != nullptr ? gp(seg->hll_lut[a])[id] : id;
+  else if (A.type == PA_AGG_DISTINCTCOUNT || A.type == PA_AGG_VALUE_HISTOGRAM)
+    out.i = seg->hll_lut[a] != nullptr ? gp(seg->hll_lut[a])[id] : id;
   else if (A.src != SRC_DOUBLE) out.i = gp(c.dict_i64)[id];
   else out.d = gp(c.dict_f64)[id];
   return out;
@@ -417,6 +426,8 @@ __device__ __forceinline__ void update_one(const DevAgg& A, int64_t key, const A
     acc.max_hll(A, key, (uint32_t)v.i);
   } else if (A.type == PA_AGG_DISTINCTCOUNT) {
     acc.set_presence(A, key, v.i);
+  } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
+    acc.add_hist(A, key, v.i);
   } else if (A.type == PA_AGG_SUM) {
     if (A.src == SRC_INT) {
       acc.add_i64(A, key, v.i);
@@ -434,7 +445,8 @@ __device__ __forceinline__ void update_one(const DevAgg& A, int64_t key, const A
 }
 
 // One aggregation update of group `key` in the workgroup's LDS accumulators (STRAT_LDS layout: DevAgg::lds_off), through
-// address-space-3 pointers (ds_* atomics). v: AggValue of agg_value (HLL: register << 8 | rank; DISTINCTCOUNT: value id).
+// address-space-3 pointers (ds_* atomics). v: AggValue of agg_value (HLL: register << 8 | rank; DISTINCTCOUNT and
+// VALUE_HISTOGRAM: value id).
 __device__ __forceinline__ void lds_update(int type, int src, int log2m, int64_t nvals, uint32_t off,
                                            unsigned char* lds, int64_t key, const AggValue& v) {
   unsigned char* b = lds + off;
@@ -464,6 +476,9 @@ __device__ __forceinline__ void lds_update(int type, int src, int log2m, int64_t
       break;
     case PA_AGG_DISTINCTCOUNT:
       ((__attribute__((address_space(3))) uint8_t*)lds_ptr(b))[key * nvals + v.i] = 1;
+      break;
+    case PA_AGG_VALUE_HISTOGRAM:
+      __hip_atomic_fetch_add(lds_ptr(b) + (key * nvals + v.i), 1u, WG_RLX);
       break;
     default: break;
   }
@@ -2877,6 +2892,9 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
       } else if (A.type == PA_AGG_DISTINCTCOUNT) {
         uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
         for (int64_t k = threadIdx.x; k < K * A.nvals / 4; k += WGS) r[k] = 0;
+      } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
+        uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
+        for (int64_t k = threadIdx.x; k < K * A.nvals; k += WGS) r[k] = 0;
       } else {
         int64_t* r = (int64_t*)(lds_acc + A.lds_off);
         const int64_t init = A.type == PA_AGG_MIN ? INT64_MAX : (A.type == PA_AGG_MAX ? INT64_MIN : 0);  // SUM, COUNT_MV: 0
@@ -3167,6 +3185,16 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
           default: break;
         }
       }
+    }
+    // VALUE_HISTOGRAM: a row can hold tens of thousands of bins, so the workgroup's threads walk the bins of all keys
+    // (not one thread per key): every non-zero u32 bin becomes one u64 add into the global block
+    for (int a = 0; a < q->num_aggs; ++a) {
+      const DevAgg& A = q->aggs[a];
+      if (A.type != PA_AGG_VALUE_HISTOGRAM) continue;
+      const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off);
+      AS1 unsigned long long* g = gp((unsigned long long*)A.acc_i64);
+      for (int64_t i = threadIdx.x; i < K * A.nvals; i += WGS)
+        if (r[i] != 0) __hip_atomic_fetch_add(g + i, (unsigned long long)r[i], RLX);
     }
   }
 }

@@ -9,7 +9,7 @@ Host-side mirror of the Java operator layer that stays in the JVM in a real inte
 It resolves predicates per segment (predicate.py), builds the table-wide group-key dictionaries (the value-keyed
 merge GroupByCombineOperator performs with IndexedTable.upsert), and decodes the GPU's accumulators into the
 reference's intermediate results: COUNT -> long, SUM/MIN/MAX -> double, AVG -> (sum, count),
-DISTINCTCOUNTHLL -> HyperLogLog.
+DISTINCTCOUNTHLL -> HyperLogLog, PERCENTILE -> ValueHistogram (the DoubleArrayList as a multiset).
 """
 import ctypes
 import dataclasses
@@ -115,6 +115,54 @@ class MinMaxRangePair:
     """MinMaxRangeAggregationFunction intermediate result (MinMaxRangePair: min, max; empty = (+inf, -inf))."""
     min: float
     max: float
+
+
+class ValueHistogram:
+    """PercentileAggregationFunction / PercentileMVAggregationFunction intermediate result: the reference's
+    DoubleArrayList of every aggregated value, held as a multiset: `values` float64 strictly ascending, `counts` int64
+    (> 0) how often each was aggregated. merge = DoubleArrayList.addAll = counts added per value; the final result is
+    the value at the percentile's rank of the sorted list."""
+    __slots__ = ("values", "counts")
+
+    def __init__(self, values=(), counts=()):
+        self.values = np.asarray(values, dtype=np.float64)
+        self.counts = np.asarray(counts, dtype=np.int64)
+        assert self.values.shape == self.counts.shape and self.values.ndim == 1
+
+    @classmethod
+    def from_values(cls, values):
+        """The multiset of a sequence of values."""
+        v, c = np.unique(np.asarray(values, dtype=np.float64), return_counts=True)
+        return cls(v, c)
+
+    @property
+    def total(self):
+        return int(self.counts.sum())
+
+    def merge(self, other):
+        if not len(other.values):
+            return ValueHistogram(self.values, self.counts)
+        v, inv = np.unique(np.concatenate([self.values, other.values]), return_inverse=True)
+        c = np.zeros(len(v), dtype=np.int64)
+        np.add.at(c, inv, np.concatenate([self.counts, other.counts]))
+        return ValueHistogram(v, c)
+
+    def value_at(self, percentile):
+        """PercentileAggregationFunction.extractFinalResult: -inf (DEFAULT_FINAL_RESULT) for no values, else the sorted
+        values' element size - 1 at 100, (int) ((long) size * percentile / 100) otherwise."""
+        size = self.total
+        if size == 0:
+            return float("-inf")
+        rank = size - 1 if percentile == 100 else int(float(size) * float(percentile) / 100)
+        rank = min(rank, size - 1)
+        return float(self.values[int(np.searchsorted(np.cumsum(self.counts), rank, side="right"))])
+
+    def __eq__(self, other):
+        return (isinstance(other, ValueHistogram) and np.array_equal(self.values, other.values) and
+                np.array_equal(self.counts, other.counts))
+
+    def __repr__(self):
+        return "ValueHistogram(%d values, %d distinct)" % (self.total, len(self.values))
 
 
 @dataclass
@@ -317,13 +365,21 @@ class GpuQueryExecutor:
                 if not all(sg.column(a.column).has_dictionary for sg in self.segs):
                     raise UnsupportedQuery("%s on a raw (no-dictionary) column %s" % (fn, a.column))
                 self.agg_map.append(acc_index((L.PA_AGG_DISTINCTCOUNT, ids[a.column], 0)))
+            elif fn in Q.PERCENTILE_FUNCTIONS:
+                # one value histogram per column, whatever percentiles of it the query asks for
+                if not all(sg.column(a.column).has_dictionary for sg in self.segs):
+                    raise UnsupportedQuery("%s on a raw (no-dictionary) column %s" % (fn, a.column))
+                if seg0.column(a.column).data_type not in ("INT", "LONG", "FLOAT", "DOUBLE"):
+                    raise UnsupportedQuery("%s on the %s column %s" % (fn, seg0.column(a.column).data_type, a.column))
+                self.agg_map.append(acc_index((L.PA_AGG_VALUE_HISTOGRAM, ids[a.column], 0)))
             else:
                 raise UnsupportedQuery("aggregation %s" % fn)
         if len(self.pa_aggs) > L.PA_MAX_AGGS:
             raise UnsupportedQuery("too many aggregations")
         spec.num_aggs = len(self.pa_aggs)
         names = {cid: name for name, cid in ids.items()}
-        # DISTINCTCOUNT: the table-wide value dictionary of the column (presence byte j <=> value value_dicts[j])
+        # DISTINCTCOUNT: the table-wide value dictionary of the column (presence byte j <=> value value_dicts[j]);
+        # PERCENTILE's value histogram: the same dictionary (bin j <=> value value_dicts[j])
         self.value_dicts = {}
         for i, (t, cid, log2m) in enumerate(self.pa_aggs):
             spec.aggs[i].type = t
@@ -331,7 +387,7 @@ class GpuQueryExecutor:
             spec.aggs[i].log2m = log2m
             if t == L.PA_AGG_SUM and names.get(cid) in self.wide_sum_columns:
                 spec.aggs[i].flags = L.PA_AGGF_WIDE_SUM
-            if t == L.PA_AGG_DISTINCTCOUNT:
+            if t in (L.PA_AGG_DISTINCTCOUNT, L.PA_AGG_VALUE_HISTOGRAM):
                 name = names[cid]
                 if name in self.table_value_dicts:
                     vd = np.asarray(self.table_value_dicts[name])
@@ -460,7 +516,7 @@ class GpuQueryExecutor:
                 if d is vd or (len(d) == len(vd) and np.array_equal(d, vd)):
                     continue
                 if not np.isin(d, vd).all():
-                    raise ValueError("DISTINCTCOUNT value dictionary misses values of a bound segment")
+                    raise ValueError("table-wide value dictionary misses values of a bound segment")
                 rm = np.searchsorted(vd, d).astype(np.int32)
                 self._keep.append(rm)
                 L.check(lib.pa_query_bind_value_remap(self.handle, si, i, rm.ctypes.data), "pa_query_bind_value_remap")
@@ -553,6 +609,9 @@ class GpuQueryExecutor:
                     o = alloc(i, cap << log2m, np.uint8)
                 elif t == L.PA_AGG_DISTINCTCOUNT:
                     o = alloc(i, cap * self._presence_stride(i), np.uint8)
+                elif t == L.PA_AGG_VALUE_HISTOGRAM:
+                    outs.append(None)  # (pa_query_fetch writes nothing: fetch_histograms / percentiles read the bins)
+                    continue
                 else:
                     o = alloc(i, cap, np.float64)
                 outs.append(o)
@@ -562,7 +621,8 @@ class GpuQueryExecutor:
             if n <= cap:
                 break
             cap = n
-        outs = [o[: n << self.pa_aggs[i][2]] if self.pa_aggs[i][0] == L.PA_AGG_DISTINCTCOUNTHLL else
+        outs = [None if o is None else
+                o[: n << self.pa_aggs[i][2]] if self.pa_aggs[i][0] == L.PA_AGG_DISTINCTCOUNTHLL else
                 (o[: n * self._presence_stride(i)] if self.pa_aggs[i][0] == L.PA_AGG_DISTINCTCOUNT else o[:n])
                 for i, o in enumerate(outs)]
         return (keys[:n] if kw == 1 else keys[:2 * n].reshape(n, 2)), counts[:n], outs
@@ -570,6 +630,60 @@ class GpuQueryExecutor:
     def _presence_stride(self, i):
         """DISTINCTCOUNT presence bytes per group: the value count rounded up to 16 (PA_ACC_PRESENCE_U8)."""
         return (len(self.value_dicts[i]) + 15) & ~15
+
+    def fetch_histograms(self, pi, num_groups, stream=None):
+        """One ValueHistogram per fetched group (fetch_arrays' order) of value-histogram accumulator `pi`: the non-zero
+        bins, compacted on the GPU (pa_query_fetch_histogram), as values of the table-wide value dictionary.
+        Synchronises `stream`."""
+        lib = L.lib()
+        vd = np.asarray(self.value_dicts[pi], dtype=np.float64)
+        n = int(num_groups)
+        ends = np.zeros(max(n, 1), dtype=np.int64)
+        total = L.check(lib.pa_query_fetch_histogram(self.handle, stream, pi, n, 0, ends.ctypes.data, None, None),
+                        "pa_query_fetch_histogram")
+        ids = OUTPUT_POOL.array("hist_ids", max(total, 1), np.int32)
+        cnt = OUTPUT_POOL.array("hist_counts", max(total, 1), np.int64)
+        if total:
+            L.check(lib.pa_query_fetch_histogram(self.handle, stream, pi, n, total, ends.ctypes.data, ids.ctypes.data,
+                                                 cnt.ctypes.data), "pa_query_fetch_histogram")
+        values, counts = vd[ids[:total]], cnt[:total].copy()
+        starts = np.concatenate([[0], ends[:n]])
+        return [ValueHistogram(values[starts[g]:starts[g + 1]], counts[starts[g]:starts[g + 1]]) for g in range(n)]
+
+    def percentiles(self, stream=None):
+        """The final values of every PERCENTILE / PERCENTILEMV aggregation of the query for every fetched group, selected
+        on the GPU without moving the bins (pa_query_percentiles: one rank select per group; the percentiles of one
+        column share a pass) — the single-server and server-trim fast path. Returns (keys, {aggregation index:
+        float64[groups]}) with keys as fetch_arrays gives them; a group without values gives -inf
+        (PercentileAggregationFunction.DEFAULT_FINAL_RESULT). Synchronises `stream`."""
+        lib = L.lib()
+        q = self.query
+        by_acc = {}
+        for ai, (a, pi) in enumerate(zip(q.aggregations, self.agg_map)):
+            if a.function in Q.PERCENTILE_FUNCTIONS:
+                by_acc.setdefault(pi, []).append(ai)
+        if self.handle is None or not by_acc:
+            return np.zeros(0, dtype=np.int64), {ai: np.zeros(0) for ais in by_acc.values() for ai in ais}
+        n = L.check(lib.pa_query_fetch(self.handle, stream, 0, None, None, None), "pa_query_fetch")
+        n = max(n, 0 if q.group_by else 1)
+        keys = np.zeros(max(n, 1), dtype=np.int64)
+        counts = np.zeros(max(n, 1), dtype=np.int64)
+        if n:
+            L.check(lib.pa_query_fetch(self.handle, stream, n, keys.ctypes.data, counts.ctypes.data, None),
+                    "pa_query_fetch")
+        out = {}
+        for pi, ais in by_acc.items():
+            ps = np.array([q.aggregations[ai].percentile for ai in ais], dtype=np.float64)
+            ids = np.full(max(n, 1) * len(ps), -1, dtype=np.int32)
+            if n:
+                L.check(lib.pa_query_percentiles(self.handle, stream, pi, n, len(ps), ps.ctypes.data, ids.ctypes.data),
+                        "pa_query_percentiles")
+            ids = ids[:n * len(ps)].reshape(n, len(ps))
+            vd = np.asarray(self.value_dicts[pi], dtype=np.float64)
+            for j, ai in enumerate(ais):
+                col = ids[:, j]
+                out[ai] = np.where(col >= 0, vd[np.maximum(col, 0)], -np.inf)
+        return keys[:n], out
 
     def key_values(self, keys):
         """Keys -> one value array per group-by column (DictionaryBasedGroupKeyGenerator.getKeys). Direct key space:
@@ -696,6 +810,7 @@ class GpuQueryExecutor:
                 stream, res.num_docs_scanned)
         key_cols = [kc.tolist() for kc in self.key_values(keys)]
         cols = []  # one python list per query aggregation
+        hists = {}
         for a, pi in zip(q.aggregations, self.agg_map):
             if a.function == "COUNT":
                 cols.append(counts.tolist())
@@ -711,6 +826,12 @@ class GpuQueryExecutor:
                 cols.append([HyperLogLog(log2m, regs[r]) for r in range(n)])
             elif a.function in ("MINMAXRANGE", "MINMAXRANGEMV"):
                 cols.append([MinMaxRangePair(lo, hi) for lo, hi in zip(outs[pi[0]].tolist(), outs[pi[1]].tolist())])
+            elif a.function in Q.PERCENTILE_FUNCTIONS:
+                # the DoubleArrayList of Percentile(MV)AggregationFunction as a multiset; aggregations of one column
+                # share the accumulator, so its groups are fetched once
+                if pi not in hists:
+                    hists[pi] = self.fetch_histograms(pi, n, stream)
+                cols.append(hists[pi])
             elif a.function in Q.DISTINCT_SET_FUNCTIONS:
                 # the value set of BaseDistinctAggregateAggregationFunction (DISTINCTCOUNT / DISTINCTSUM / DISTINCTAVG)
                 vd = self.value_dicts[pi]
@@ -745,7 +866,8 @@ class GpuQueryExecutor:
                            ("COUNT", "SUM", "MIN", "MAX") else
                            AvgPair(0.0, 0) if fn == "AVG" else
                            HyperLogLog(a.log2m) if fn in ("DISTINCTCOUNTHLL", "DISTINCTCOUNTRAWHLL") else
-                           MinMaxRangePair(float("inf"), float("-inf")) if fn == "MINMAXRANGE" else set())
+                           MinMaxRangePair(float("inf"), float("-inf")) if fn == "MINMAXRANGE" else
+                           ValueHistogram() if fn == "PERCENTILE" else set())
             res.row = row
         return res
 

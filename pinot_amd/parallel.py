@@ -25,6 +25,7 @@ SECTION_OP = {
     L.PA_ACC_HLL_U8: dist.ReduceOp.MAX,
     L.PA_ACC_DOCS_U64: dist.ReduceOp.SUM,
     L.PA_ACC_PRESENCE_U8: dist.ReduceOp.MAX,  # DISTINCTCOUNT value presence bytes (set union)
+    L.PA_ACC_HIST_U64: dist.ReduceOp.SUM,  # PERCENTILE value histogram bins (DoubleArrayList.addAll)
     L.PA_ACC_KEYS_I64: None,  # not element-wise reducible (hashed key spaces)
 }
 SECTION_DTYPE = {
@@ -37,6 +38,7 @@ SECTION_DTYPE = {
     L.PA_ACC_HLL_U8: torch.uint8,  # one byte per register (HyperLogLog.addAll == register max)
     L.PA_ACC_DOCS_U64: torch.int64,
     L.PA_ACC_PRESENCE_U8: torch.uint8,
+    L.PA_ACC_HIST_U64: torch.int64,
     L.PA_ACC_KEYS_I64: torch.int64,
 }
 # identity of each per-key section (what pa_query_reset leaves in an empty slot)
@@ -288,7 +290,7 @@ class TableLayout:
                     hash_keys_bound=self.hash_keys_bound, schema=self.schema)
 
 
-from .query import DISTINCT_SET_FUNCTIONS as DISTINCT_FUNCTIONS, query_columns  # noqa: E402
+from .query import DISTINCT_SET_FUNCTIONS as DISTINCT_FUNCTIONS, PERCENTILE_FUNCTIONS, query_columns  # noqa: E402
 
 
 def _encode_record(rec):
@@ -380,7 +382,7 @@ def table_layout(query, segments, group=None):
         if ds:
             local["dicts"][name] = np.unique(np.concatenate(ds))
     for a in query.aggregations:
-        if a.function in DISTINCT_FUNCTIONS and a.column not in local["vals"]:
+        if a.function in DISTINCT_FUNCTIONS + PERCENTILE_FUNCTIONS and a.column not in local["vals"]:
             ds = [s.column(a.column).dictionary for s in segments if s.column(a.column).has_dictionary]
             if ds:
                 local["vals"][a.column] = np.unique(np.concatenate(ds))

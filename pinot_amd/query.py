@@ -10,8 +10,9 @@ REGEXP_LIKE / LIKE become RegexpLikePredicate as in RequestContextUtils.java:231
 Comparison predicates become RangePredicate exactly as the reference's RequestContextUtils does
 (pinot-common/.../request/context/RequestContextUtils.java: >, >=, <, <=, BETWEEN -> RANGE).
 Aggregations: COUNT(*), SUM, MIN, MAX, AVG, MINMAXRANGE, DISTINCTCOUNT, DISTINCTSUM, DISTINCTAVG, DISTINCTCOUNTHLL(col[, log2m]), DISTINCTCOUNTRAWHLL(col[, log2m]) and their *MV
-forms.
+forms; PERCENTILE<digits>(col), PERCENTILE<digits>MV(col), PERCENTILE(col, p), PERCENTILEMV(col, p).
 """
+import decimal
 import re
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
@@ -157,6 +158,24 @@ BITMAP_FUNCTIONS = ("DISTINCTCOUNTBITMAP", "DISTINCTCOUNTBITMAPMV")
 HLL_FUNCTIONS = ("DISTINCTCOUNTHLL", "DISTINCTCOUNTHLLMV", "DISTINCTCOUNTRAWHLL", "DISTINCTCOUNTRAWHLLMV")
 
 
+# PercentileAggregationFunction / PercentileMVAggregationFunction: the intermediate result is every aggregated value (a
+# DoubleArrayList; here a value histogram, engine.ValueHistogram), the final result the value at the percentile's rank
+PERCENTILE_FUNCTIONS = ("PERCENTILE", "PERCENTILEMV")
+_PERCENTILE_ONE_ARG = re.compile(r"(\d+)(MV)?$")
+
+
+def java_double_string(x):
+    """Double.toString of a finite double: the shortest digits that round-trip (Python's repr gives the same digits),
+    plain notation from 1e-3 up to 1e7, computerized scientific notation (1.0E-5) outside."""
+    x = float(x)
+    if x == 0 or 1e-3 <= abs(x) < 1e7:
+        return repr(x)  # (repr is plain from 1e-4 up to 1e16)
+    sign, digits, exp = decimal.Decimal(repr(x)).as_tuple()
+    digits = "".join(map(str, digits)).rstrip("0") or "0"
+    exp10 = len(decimal.Decimal(repr(x)).as_tuple()[1]) + exp - 1
+    return "%s%s.%sE%d" % ("-" if sign else "", digits[0], digits[1:] or "0", exp10)
+
+
 def base_function(fn):
     """Merge/extract semantics of a function: the *MV forms behave like their single-value form, COUNTMV like COUNT."""
     return fn[:-2] if fn.endswith("MV") else fn
@@ -167,12 +186,21 @@ class Aggregation:
     function: str              # COUNT SUM MIN MAX AVG DISTINCTCOUNTHLL and the *MV forms
     column: Optional[str] = None
     log2m: int = DEFAULT_HLL_LOG2M
+    percentile: float = -1.0   # PERCENTILE / PERCENTILEMV: 0..100
+    version: int = 0           # PERCENTILE spelling: 0 = PERCENTILE<digits>(col), 1 = PERCENTILE(col, p)
 
     @property
     def result_name(self):
         """AggregationFunction.getResultColumnName: lower-case function name + (column)."""
         if self.function == "COUNT":
             return "count(*)"
+        if self.function in PERCENTILE_FUNCTIONS:
+            # Percentile(MV)AggregationFunction.getResultColumnName: percentile50(c) / percentile50mv(c) for the
+            # one-argument spelling, percentile(c, 50.0) / percentilemv(c, 50.0) (Double.toString) for the other
+            mv = "mv" if self.function.endswith("MV") else ""
+            if self.version == 0:
+                return "percentile%d%s(%s)" % (int(self.percentile), mv, self.column)
+            return "percentile%s(%s, %s)" % (mv, self.column, java_double_string(self.percentile))
         return "%s(%s)" % (self.function.lower(), self.column)
 
 
@@ -307,6 +335,8 @@ class _Parser:
             self.expect_op("*")
             self.expect_op(")")
             return Aggregation("COUNT")
+        if fn.startswith("PERCENTILE"):
+            return self.percentile(fn)
         col = self.ident()
         log2m = DEFAULT_HLL_LOG2M
         if self.op(","):
@@ -315,6 +345,27 @@ class _Parser:
         if fn not in SUPPORTED_FUNCTIONS:
             raise ValueError("unsupported aggregation %s" % fn)
         return Aggregation(fn, col, log2m)
+
+    def percentile(self, fn):
+        """AggregationFunctionFactory.java:66-175 for the exact percentile: PERCENTILE<digits>(col) and
+        PERCENTILE<digits>MV(col) (version 0), PERCENTILE(col, p) and PERCENTILEMV(col, p) (version 1, p a number or a
+        quoted number); every other PERCENTILE* name (EST, TDIGEST, KLL, RAW...) is not on this path."""
+        rest = fn[len("PERCENTILE"):]
+        col = self.ident()
+        args = []
+        while self.op(","):
+            args.append(self.literal())
+        self.expect_op(")")
+        one = _PERCENTILE_ONE_ARG.match(rest)
+        if not args and one:
+            p, version, mv = float(int(one.group(1))), 0, one.group(2)
+        elif len(args) == 1 and rest in ("", "MV"):
+            p, version, mv = float(args[0]), 1, rest
+        else:
+            raise ValueError("unsupported aggregation %s" % fn)
+        if not 0 <= p <= 100:  # (Preconditions.checkArgument in the factory; NaN fails it too)
+            raise ValueError("Invalid percentile: %s" % java_double_string(p))
+        return Aggregation("PERCENTILEMV" if mv else "PERCENTILE", col, percentile=p, version=version)
 
     def filter_or(self):
         left = self.filter_and()

@@ -2,7 +2,8 @@
 
   merge_intermediate   ~ GroupByDataTableReducer / AggregationDataTableReducer merging server DataTables
                          (AggregationFunction.merge: COUNT/SUM +, MIN min, MAX max, AVG pair +, HLL addAll,
-                         MINMAXRANGE pair min/max, DISTINCTCOUNT / DISTINCTSUM / DISTINCTAVG set union)
+                         MINMAXRANGE pair min/max, DISTINCTCOUNT / DISTINCTSUM / DISTINCTAVG set union,
+                         PERCENTILE addAll = value histogram counts added)
   server_trim          ~ IndexedTable.finish on the server (IndexedTable.java:149): with ORDER BY keep the top
                          max(limit*5, minServerGroupTrimSize) groups (GroupByUtils.getTableCapacity); without
                          ORDER BY keep `limit` groups (GroupByCombineOperator.java:63-73)
@@ -33,11 +34,21 @@ def merge_value(fn, a, b):
     if fn in ("DISTINCTCOUNT", "DISTINCTSUM", "DISTINCTAVG", "DISTINCTCOUNTBITMAP"):
         # BaseDistinctAggregateAggregationFunction.merge: union (DISTINCTCOUNTBITMAP: RoaringBitmap.or)
         return set(a) | set(b)
+    if fn == "PERCENTILE":  # PercentileAggregationFunction.merge: DoubleArrayList.addAll (counts add per value)
+        return a.merge(b)
     raise ValueError(fn)
 
 
 def final_value(fn, v):
-    fn = Q.base_function(fn)
+    """extractFinalResult. fn: the function's name, or the Aggregation (PERCENTILE needs its percentile)."""
+    agg = fn if isinstance(fn, Q.Aggregation) else None
+    fn = Q.base_function(agg.function if agg is not None else fn)
+    if fn == "PERCENTILE":
+        # PercentileAggregationFunction.extractFinalResult: -inf (DEFAULT_FINAL_RESULT) for an empty list, else the
+        # sorted values' element at the percentile's rank (engine.ValueHistogram.value_at)
+        if agg is None:
+            raise ValueError("PERCENTILE's final value needs the Aggregation (its percentile), not the name")
+        return v.value_at(agg.percentile)
     if fn == "AVG":
         return v.sum / v.count if v.count else -math.inf
     if fn == "DISTINCTCOUNTHLL":
@@ -129,7 +140,7 @@ def _order_key_fn(query):
 def server_trim(res: IntermediateResult, query: Q.Query) -> IntermediateResult:
     if not query.group_by:
         return res
-    fns = [a.function for a in query.aggregations]
+    fns = list(query.aggregations)
     if query.order_by:
         trim = max(query.limit * 5, query.min_server_group_trim_size)
     else:
@@ -152,7 +163,7 @@ def server_trim(res: IntermediateResult, query: Q.Query) -> IntermediateResult:
 
 def final_result_table(res: IntermediateResult, query: Q.Query):
     """Broker ResultTable rows: [select group-by columns..., final aggregation values...]."""
-    fns = [a.function for a in query.aggregations]
+    fns = list(query.aggregations)
     nsel = query.num_select_aggs if query.num_select_aggs >= 0 else len(fns)
     if not query.group_by:
         return [[final_value(f, v) for f, v in zip(fns, res.row)][:nsel]]
