@@ -506,6 +506,16 @@ int32_t pa_query_dense_packed(const pa_query* q);
  * region; pass C reads every partition through its chunk list: no count pass), 2 when it also runs the count-free H
  * emit (DISTINCTCOUNTHLLMV next to the V stream), 0 otherwise, <0 if not prepared. */
 int32_t pa_query_count_free_emit(const pa_query* q);
+/* 1 when some segment's plan carries the equality prefilter of the lane-major scan (a single `column = value` literal
+ * on a staged column of up to 24 bits): in the scan's hoisted steady-state loop whole tiles are first asked "any match?"
+ * on the packed stream words. Tiles outside that loop (a wave's first tiles, a segment's ragged last tile, tiles at a
+ * segment crossing) take the per-doc leaf as before. 0 otherwise, <0 if not prepared. */
+int32_t pa_query_eq_prefilter(const pa_query* q);
+/* 1 when the plan sets the nt cache policy for the staged column streams of the lane-major scan's hoisted steady-state
+ * loops (by default only a launch that stages more than L2 + Infinity Cache hold). Tiles issued outside those loops (a
+ * wave's first tiles, segment crossings, a PA_QF_DEBUG_STREAM_ONLY run) keep the default policy. 0 otherwise, <0 if
+ * not prepared. */
+int32_t pa_query_stream_nt(const pa_query* q);
 /* Keys per partition of the partitioned plan's V stream (a power of two, or under the count-free emit any count that
  * spreads the key space over whole rounds of pass C's workgroups), 0 when the plan is not partitioned, <0 if not
  * prepared. */

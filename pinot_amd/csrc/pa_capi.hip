@@ -157,6 +157,7 @@ int pa_query_prepare(pa_query* q) {
   const int wpw = q->partitioned ? scan_waves(q->emit_strat) : scan_waves(q->strategy);
   const int64_t want = (total_tiles + wpw - 1) / wpw;
   q->grid = (int)std::max<int64_t>(1, std::min(max_wg, want));
+  if (q->tune.scan_grid > 0 && !q->partitioned) q->grid = (int)std::min<int64_t>(q->grid, q->tune.scan_grid);
 
   if (q->partitioned) {
     // the count pass: the same tiles, waves and grid; only the group-by and filter columns staged
@@ -220,8 +221,43 @@ int64_t pa_query_num_keys(const pa_query* q) { return q ? q->num_keys : -1; }
 int pa_query_reset(pa_query* q, void* stream) {
   if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
   hipStream_t st = (hipStream_t)stream;
-  // one memset of the whole accumulator block, then the MIN/MAX sections to their identities
-  PA_HIP(hipMemsetAsync(q->external_acc ? q->external_acc : q->acc.p, 0, q->acc.n, st));
+  char* block = (char*)(q->external_acc ? q->external_acc : q->acc.p);
+  // Small blocks (the common case): one launch writes zeros and identities (the block is whole 256-byte units). Larger
+  // ones keep the memsets, whose rate matters there and whose extra launches no longer do.
+  auto identity = [](const Section& sc, int64_t& v) {
+    if (sc.kind == PA_ACC_MIN_I64 || sc.kind == PA_ACC_KEYS_I64) v = INT64_MAX;
+    else if (sc.kind == PA_ACC_MAX_I64) v = INT64_MIN;
+    else return false;
+    return true;
+  };
+  const bool fused = q->tune.reset_fused < 0 ? q->acc.n <= kResetFusedMaxBytes : q->tune.reset_fused != 0;
+  if (fused) {
+    ResetArgs a{};
+    a.block = (int64_t*)block;
+    a.block_words = (int64_t)(q->acc.n / 8);
+    if (q->hq.leap_mode) {
+      a.header = (int64_t*)q->leap_buf.p;
+      a.header_words = (int64_t)(leap_header_bytes(q) / 8);
+    }
+    bool fits = true;
+    for (const Section& sc : q->sections) {
+      int64_t v;
+      if (!identity(sc, v)) continue;
+      if (a.num_sections == ResetArgs::kMaxSections) {
+        fits = false;
+        break;
+      }
+      a.sec[a.num_sections].first = ((char*)sc.ptr - block) / 8;
+      a.sec[a.num_sections].n = sc.n;
+      a.sec[a.num_sections].value = v;
+      ++a.num_sections;
+    }
+    if (fits) {
+      PA_HIP(launch_reset(a, st));
+      return PA_OK;
+    }
+  }
+  PA_HIP(hipMemsetAsync(block, 0, q->acc.n, st));
   if (q->hq.leap_mode) PA_HIP(hipMemsetAsync(q->leap_buf.p, 0, leap_header_bytes(q), st));
   for (const Section& sc : q->sections) {
     if (sc.kind == PA_ACC_MIN_I64 || sc.kind == PA_ACC_KEYS_I64) PA_HIP(launch_fill_i64((int64_t*)sc.ptr, sc.n, INT64_MAX, st));
@@ -425,6 +461,8 @@ int pa_query_plan(const pa_query* q, int32_t* strategy, int32_t* steps, int32_t*
 int32_t pa_query_num_eager_literals(const pa_query* q) { return q && q->prepared ? q->num_eager : -1; }
 
 int32_t pa_query_lane_major(const pa_query* q) { return q && q->prepared ? q->lane_major : -1; }
+int32_t pa_query_eq_prefilter(const pa_query* q) { return q && q->prepared ? q->eq_prefilter : -1; }
+int32_t pa_query_stream_nt(const pa_query* q) { return q && q->prepared ? q->stream_nt : -1; }
 int32_t pa_query_count_free_emit(const pa_query* q) { return q && q->prepared ? (q->pve.fn ? (q->pvh.fn ? 2 : 1) : 0) : -1; }
 int32_t pa_query_partition_keys(const pa_query* q) {
   if (!q || !q->prepared) return -1;

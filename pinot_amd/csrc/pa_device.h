@@ -442,7 +442,8 @@ struct LmSegPlan {
   int32_t num_docs;          // 2
   int32_t num_wtiles;        // 3
   uint32_t dummy_lo, dummy_hi;  // 4,5: readable address for the DMA padding instructions
-  int32_t pad0[2];           // 6,7
+  uint32_t flags;            // 6: kLmEqPrefilter | kLmStreamNt (the hoisted loops of scan_kernel)
+  int32_t pad0;              // 7
   struct {                   // 8 + 4c
     uint32_t lo, hi;         // stream words (past the guard words)
     int32_t nbits;
@@ -456,8 +457,14 @@ struct LmSegPlan {
     int32_t flags;           // bit 0: negate, bit 1: closes a CNF clause
     uint32_t lut_lo, lut_hi; // DICT_SET bitmap
   } lf[kLmEager];
-  int32_t pad1[8];           // 56..63
+  uint32_t eq_win_lo, eq_win_hi;  // 56,57: kLmEqPrefilter: the leaf's dictId repeated every nbits bits (pa_eq_any.h)
+  int32_t pad1[6];           // 58..63
 };
+constexpr uint32_t kLmEqPrefilter = 1u;  // lf[0] is an equality: whole tiles ask eq_any first
+constexpr uint32_t kLmStreamNt = 2u;     // the staged columns' LDS-DMAs carry the nt policy
+// The widest column the equality prefilter takes: it issues 5 vector instructions per stream word (nbits words per
+// lane) against leaf_lm's ~4 per doc (32 docs), so beyond 24 bits nothing is left to gain.
+constexpr int kEqPrefilterMaxNb = 24;
 static_assert(sizeof(LmSegPlan) == 256, "one dword per lane");
 
 // Order-preserving int64 image of an IEEE double (an involution): signed int64 order == double order.

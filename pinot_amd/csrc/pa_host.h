@@ -141,6 +141,11 @@ constexpr int64_t kDirectMaxKeys = int64_t(1) << 27;  // direct-indexed key spac
 constexpr uint64_t kMaxHashSlots = uint64_t(1) << 28;
 constexpr uint64_t kWalkMaxBitmapBytes = uint64_t(4) << 30;  // numGroupsLimit walk: admitted-key bitmaps of a query
 constexpr size_t kLdsBudget = 160 * 1024;
+// pa_query_reset: accumulator blocks up to this size are reset by one kernel launch (reset_kernel), larger ones by
+// memsets + fills. Measured on MIN + MAX + SUM blocks of 8 KiB .. 8 MiB (profiles/reset_sizes.jsonl): one launch
+// 3.0-3.2 us up to 4 MiB and 3.9 us at 8 MiB, against 7.6-8.0 us for the memset + two fills at every size; 8 MiB is the
+// largest block measured, so the bound stops there.
+constexpr size_t kResetFusedMaxBytes = size_t(8) << 20;
 
 struct Section {
   int32_t kind;
@@ -233,6 +238,8 @@ struct pa_query {
   DevBuf fetch_blocks, fetch_stage;  // large-key fetch: per-block counts / compacted rows
   void* fetch_host = nullptr;        // pinned copy of the compacted rows
   int lane_major = 0;
+  int eq_prefilter = 0;  // some segment's plan takes the equality prefilter (LmSegPlan::flags)
+  int stream_nt = 0;     // the hoisted loops' column DMAs carry the nt policy
   int dense_packed = 0;  // STRAT_GDENSE_LM*: packed accumulation (GdLmPlan)
   // the dense kernel specialised to this query's shape (gdl_jit.hip, compiled by hiprtc): null = the generic kernel
   hipFunction_t jit_fn = nullptr;

@@ -1081,6 +1081,22 @@ __global__ void fill_i64_kernel(int64_t* p, int64_t n, int64_t v) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
+// Word i of the block followed by the header: the identity of the section holding it, else zero. One store per word,
+// so the zeroing and the identities cannot race.
+__global__ void __launch_bounds__(256) reset_kernel(ResetArgs a) {
+  const int64_t total = a.block_words + a.header_words;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i >= a.block_words) {
+      a.header[i - a.block_words] = 0;
+      continue;
+    }
+    int64_t v = 0;
+    for (int k = 0; k < a.num_sections; ++k)
+      if ((uint64_t)(i - a.sec[k].first) < (uint64_t)a.sec[k].n) v = a.sec[k].value;
+    a.block[i] = v;
+  }
+}
+
 // out[i*per + j] = src[keys[i]*per + j] for elements of `esize` bytes (4 or 8)
 __global__ void gather_kernel(const void* src, int esize, int64_t per, const int64_t* keys, int64_t n, void* out) {
   const int64_t total = n * per;
@@ -1886,6 +1902,11 @@ hipError_t launch_hll_lut_hashes(const int32_t* hashes, int32_t card, int32_t lo
 
 hipError_t launch_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t s) {
   fill_i64_kernel<<<grid_for(n, 256), 256, 0, s>>>(p, n, v);
+  return hipGetLastError();
+}
+
+hipError_t launch_reset(const ResetArgs& a, hipStream_t s) {
+  reset_kernel<<<grid_for(a.block_words + a.header_words, 256), 256, 0, s>>>(a);
   return hipGetLastError();
 }
 

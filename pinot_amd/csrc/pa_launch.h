@@ -94,6 +94,21 @@ hipError_t launch_hll_lut_numeric(const int64_t* di, const double* dd, int32_t v
                                   uint32_t* lut, hipStream_t s);
 hipError_t launch_hll_lut_hashes(const int32_t* hashes, int32_t card, int32_t log2m, uint32_t* lut, hipStream_t s);
 hipError_t launch_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t s);
+// pa_query_reset as one launch: the accumulator block and the leap header to zero, except the block's MIN / MAX / KEYS
+// sections, which take their identities (every range in 8-byte words; the table travels by value)
+struct ResetArgs {
+  static constexpr int kMaxSections = 24;  // (at most one per aggregation + the hashed keys)
+  int64_t* block;
+  int64_t block_words;
+  int64_t* header;  // null: no leap header
+  int64_t header_words;
+  int32_t num_sections;
+  struct {
+    int64_t first, n;  // words of the block
+    int64_t value;
+  } sec[kMaxSections];
+};
+hipError_t launch_reset(const ResetArgs& a, hipStream_t s);
 hipError_t launch_gather(const void* src, int esize, int64_t per, const int64_t* keys, int64_t n, void* out,
                          hipStream_t s);
 // partitioned aggregation: per-(workgroup, partition) range offsets + partition bases (after the count pass, which ran

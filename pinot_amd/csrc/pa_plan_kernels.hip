@@ -1,6 +1,7 @@
 // Query planning, second half: tile geometry, partitions, the kernel variant and occupancy, the scan descriptors,
 // scratch, numGroupsLimit buffers and the fused statistics' buffers.
 #include "pa_host.h"
+#include "pa_eq_any.h"
 
 
 TilePlan plan_tiles(const pa_query* q, const std::vector<DevSeg>& segs, int strat, bool use_lm, size_t acc_b,
@@ -1062,6 +1063,15 @@ int upload_descriptors(pa_query* q) {
       PA_HIP(hipMemcpy(q->dsegs_count.p, q->hsegs_count.data(), sizeof(DevSeg) * q->nseg, hipMemcpyHostToDevice));
   }
   q->hplans.assign(std::max(1, q->nseg), LmSegPlan{});
+  // the hoisted loops of scan_kernel<.., 32, 1> (the direct strategies; the dense kernels read the tables too, but
+  // not these flags)
+  const bool std_lm = q->lane_major && !q->partitioned && !q->limit_mode &&
+                      (q->strategy == STRAT_LDS || q->strategy == STRAT_GLOBAL || q->strategy == STRAT_LANE ||
+                       q->strategy == STRAT_LANE_CNT || q->strategy == STRAT_LANE_RAW || q->strategy == STRAT_LANE_DICT);
+  // nt: by default only a stream that cannot stay in the caches anyway (8 XCDs x 4 MiB L2 + 256 MiB Infinity Cache)
+  constexpr uint64_t kCacheBytes = (uint64_t(8) * 4 + 256) << 20;
+  q->stream_nt = std_lm && (q->tune.stream_nt < 0 ? q->staged_bytes > kCacheBytes : q->tune.stream_nt != 0) ? 1 : 0;
+  q->eq_prefilter = 0;
   if (q->lane_major) {
     for (int si = 0; si < q->nseg; ++si) {
       const DevSeg& d = q->hsegs[si];
@@ -1090,6 +1100,22 @@ int upload_descriptors(pa_query* q) {
         P.lf[li].flags = (L.negate ? 1 : 0) | (L.clause_end ? 2 : 0);
         P.lf[li].lut_lo = (uint32_t)(uintptr_t)L.lut;
         P.lf[li].lut_hi = (uint32_t)((uint64_t)(uintptr_t)L.lut >> 32);
+      }
+      if (q->stream_nt) P.flags |= kLmStreamNt;
+      // one eager DICT_RANGE leaf of span 1, not negated, closing its clause: the hoisted single-range loop asks
+      // eq_any first (the MSB-aligned span of one dictId is all ones below the value's nbits)
+      // by default only next to the nt stream, where it measured a gain; alone it measured none
+      if (std_lm && (q->tune.eq_prefilter < 0 ? q->stream_nt != 0 : q->tune.eq_prefilter != 0) && q->num_eager == 1) {
+        const DevLeaf& L = d.leaves[0];
+        const int nb = L.nbits;
+        if (L.kind == PA_LEAF_DICT_RANGE && !L.negate && L.clause_end && nb >= 1 && nb <= kEqPrefilterMaxNb &&
+            (uint32_t)L.span == (uint32_t)((uint64_t(1) << (32 - nb)) - 1)) {
+          const uint64_t win = eq_pattern_window(nb, (uint32_t)L.lo >> (32 - nb));
+          P.eq_win_lo = (uint32_t)win;
+          P.eq_win_hi = (uint32_t)(win >> 32);
+          P.flags |= kLmEqPrefilter;
+          q->eq_prefilter = 1;
+        }
       }
     }
   }

@@ -22,6 +22,7 @@
 #include "pa_device.h"
 #include "pa_launch.h"
 #include "pa_keys.h"
+#include "pa_eq_any.h"
 
 namespace pa {
 
@@ -101,38 +102,47 @@ __device__ __forceinline__ lds_u32_t* lds_ptr(const void* p) { return (lds_u32_t
 // writes from later ds_reads of OTHER ring slots and would put vmcnt(0) in front of every tile's decode,
 // draining the whole ring. Visibility is guaranteed by the explicit counted waits in wait_tile; vm ops the
 // compiler does not know about only make its own vmcnt waits stricter, never wrong.
+// NT: the load carries the `nt` cache policy (a stream read once: see stream_nt in pa_tuning.h). The modifier is part
+// of the instruction text, hence a template parameter; PA_DMA16_ASM splices it into the one copy of each block.
+#define PA_DMA16_ASM(MOD)                      \
+  "s_mov_b32 %0, m0\n\t"                       \
+  "s_mov_b32 m0, %2\n\t"                       \
+  "s_nop 0\n\t"                                \
+  "global_load_lds_dwordx4 %1, off" MOD "\n\t" \
+  "s_mov_b32 m0, %0"
+#define PA_DMA16_MASKED_ASM(MOD)               \
+  "s_mov_b64 %1, exec\n\t"                     \
+  "s_mov_b64 exec, %4\n\t"                     \
+  "s_mov_b32 %0, m0\n\t"                       \
+  "s_mov_b32 m0, %3\n\t"                       \
+  "s_nop 0\n\t"                                \
+  "global_load_lds_dwordx4 %2, off" MOD "\n\t" \
+  "s_mov_b32 m0, %0\n\t"                       \
+  "s_mov_b64 exec, %1"
+
+template <bool NT = false>
 __device__ __forceinline__ void dma16(const void* src, uint32_t lds_base) {
   uint32_t keep;
   // wave-uniform by construction; readfirstlane keeps it in an SGPR even where the compiler computed it with VALU ops
   lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_base);
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(lds_base));
+  if constexpr (NT) asm volatile(PA_DMA16_ASM(" nt") : "=&s"(keep) : "v"(src), "s"(lds_base));
+  else asm volatile(PA_DMA16_ASM("") : "=&s"(keep) : "v"(src), "s"(lds_base));
 }
 
 // dma16 for the lanes of `mask` only, with EXEC set and restored inside the asm block (no branch around a partial
 // DMA instruction; the compiler's EXEC tracking is unaffected).
+template <bool NT = false>
 __device__ __forceinline__ void dma16_masked(const void* src, uint32_t lds_base, uint64_t mask) {
   uint32_t keep;
   uint64_t save;
   lds_base = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_base);
-  asm volatile(
-      "s_mov_b64 %1, exec\n\t"
-      "s_mov_b64 exec, %4\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, off\n\t"
-      "s_mov_b32 m0, %0\n\t"
-      "s_mov_b64 exec, %1"
-      : "=&s"(keep), "=&s"(save)
-      : "v"(src), "s"(lds_base), "s"(mask));
+  if constexpr (NT)
+    asm volatile(PA_DMA16_MASKED_ASM(" nt") : "=&s"(keep), "=&s"(save) : "v"(src), "s"(lds_base), "s"(mask));
+  else
+    asm volatile(PA_DMA16_MASKED_ASM("") : "=&s"(keep), "=&s"(save) : "v"(src), "s"(lds_base), "s"(mask));
 }
+#undef PA_DMA16_ASM
+#undef PA_DMA16_MASKED_ASM
 
 template <int STEPS>
 __device__ __forceinline__ void stage_tile(const DevSeg* __restrict__ seg, int64_t wt, uint32_t* img, int lane,
@@ -2716,6 +2726,30 @@ __device__ __forceinline__ uint32_t leaf_lm_any(int nb, int kind, uint32_t regio
   }
 }
 
+// Equality prefilter of a full lane-major tile (pa_eq_any.h): non-zero iff one of the lane's 32 docs has the dictId of
+// the pattern `window`. Never a match word: a tile where no lane answers non-zero is done, any other goes through
+// leaf_lm_any as before. Widths above kEqPrefilterMaxNb (pa_device.h) are not compiled: the planner never asks.
+__device__ __forceinline__ uint32_t eq_any_lm(int nb, uint32_t region_lds, int lane, uint64_t window) {
+  // The pattern words are shifts of the window, one scalar instruction each. Opaque here, so that they are taken per
+  // tile: hoisted out of the tile loop they are nb more live scalar registers, which the kernel does not have (they
+  // came back per tile as v_readlane pairs from a spill register, vector instructions the prefilter is there to save).
+  asm volatile("" : "+s"(window));
+  switch (nb) {
+#define PA_EQ_CASE(N)                                                                                        \
+  case N: {                                                                                                  \
+    const lds_u32_t* p = (const lds_u32_t*)(uintptr_t)(region_lds + (uint32_t)lane * (uint32_t)(N * 4));     \
+    return eq_any<N>([p](int j) -> uint32_t { return p[j]; }, window);                                       \
+  }
+    PA_EQ_CASE(1) PA_EQ_CASE(2) PA_EQ_CASE(3) PA_EQ_CASE(4) PA_EQ_CASE(5) PA_EQ_CASE(6) PA_EQ_CASE(7) PA_EQ_CASE(8)
+    PA_EQ_CASE(9) PA_EQ_CASE(10) PA_EQ_CASE(11) PA_EQ_CASE(12) PA_EQ_CASE(13) PA_EQ_CASE(14) PA_EQ_CASE(15)
+    PA_EQ_CASE(16) PA_EQ_CASE(17) PA_EQ_CASE(18) PA_EQ_CASE(19) PA_EQ_CASE(20) PA_EQ_CASE(21) PA_EQ_CASE(22)
+    PA_EQ_CASE(23) PA_EQ_CASE(24)
+#undef PA_EQ_CASE
+    default: return 1u;  // (not compiled: every tile takes the leaf)
+  }
+}
+static_assert(kEqPrefilterMaxNb == 24, "eq_any_lm compiles the widths 1..kEqPrefilterMaxNb");
+
 // LDS-DMA of one wave tile of every staged column (plan table `ip`), padded to exactly D instructions.
 __device__ __forceinline__ void stage_tile_lm(uint32_t ip, int64_t wt, uint32_t img_lds, int lane, const int D) {
   const int ns = (int)rl(ip, 0);
@@ -2824,6 +2858,7 @@ struct LmIssue {
 
 // Wait for the tile in slot `slot_off`, then issue the next tile `ti` (ring slot `islot`): every instruction a full
 // 64-lane DMA except a column's lane-masked tail, padded to exactly D instructions.
+template <bool NT = false>
 __device__ __forceinline__ void lm_wait_issue(const LmIssue& I, uint32_t& slot_off, int R, int D, int64_t younger,
                                               uint32_t dst0, int64_t it, uint32_t lane_off) {
   if (R == 2) vm_wait_token<0>(slot_off);  // the one tile in flight has landed
@@ -2834,10 +2869,10 @@ __device__ __forceinline__ void lm_wait_issue(const LmIssue& I, uint32_t& slot_o
     if (c < I.nst) {
       const char* src = I.base[c] + it * I.stride[c] + lane_off;
       const uint32_t dst = dst0 + I.off[c];
-      for (int k = 0; k < I.nfull[c]; ++k) dma16(src + 1024 * k, dst + 1024 * k);
+      for (int k = 0; k < I.nfull[c]; ++k) dma16<NT>(src + 1024 * k, dst + 1024 * k);
       issued += I.nfull[c];
       if (I.tail[c]) {
-        dma16_masked(src + 1024 * I.nfull[c], dst + 1024 * I.nfull[c], I.tail[c]);
+        dma16_masked<NT>(src + 1024 * I.nfull[c], dst + 1024 * I.nfull[c], I.tail[c]);
         ++issued;
       }
     }
@@ -3010,19 +3045,29 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
             const uint32_t off0 = 4u * rl(pp, 26), lo0 = rl(pp, 27), hi0 = rl(pp, 28);
             const bool neg0 = (rl(pp, 29) & 1u) != 0;
             const int64_t full_tiles = (int64_t)(int32_t)rl(pp, 2) / kWTileDocs;
+            // the planner's per-segment choices (LmSegPlan::flags): the equality prefilter with its pattern, nt DMAs
+            const uint32_t lmf = rl(pp, 6);
+            const bool eq0 = (lmf & kLmEqPrefilter) != 0, nt = (lmf & kLmStreamNt) != 0;
+            const uint64_t eq_win = ((uint64_t)rl(pp, 57) << 32) | rl(pp, 56);
             while (t < seg_end && ti < issue_end) {
               uint32_t slot_off = (uint32_t)(pslot * img_dw);
-              lm_wait_issue(I, slot_off, R, D, ti - (t + 1), ring_lds + 4u * (uint32_t)(islot * img_dw), ti - ifirst,
-                            16u * (uint32_t)lane);
+              if (nt)
+                lm_wait_issue<true>(I, slot_off, R, D, ti - (t + 1), ring_lds + 4u * (uint32_t)(islot * img_dw),
+                                    ti - ifirst, 16u * (uint32_t)lane);
+              else
+                lm_wait_issue(I, slot_off, R, D, ti - (t + 1), ring_lds + 4u * (uint32_t)(islot * img_dw), ti - ifirst,
+                              16u * (uint32_t)lane);
               ++ti;
               islot = islot + 1 == R ? 0 : islot + 1;
               if (t - seg_first < full_tiles) {
-                uint32_t m = leaf_lm_any(nb0, PA_LEAF_DICT_RANGE, ring_lds + 4u * slot_off + off0, lane, lo0, hi0,
-                                         nullptr);
-                if (neg0) m = ~m;
-                if (__ballot(m != 0) != 0)
-                  matched += tile_survivors<STRAT, 32, 1>(q, seg, ring + slot_off, (t - seg_first) * kWTileDocs, m,
-                                                          lane, acc.lds, *acc.ps, la);
+                if (!eq0 || __ballot(eq_any_lm(nb0, ring_lds + 4u * slot_off + off0, lane, eq_win) != 0) != 0) {
+                  uint32_t m = leaf_lm_any(nb0, PA_LEAF_DICT_RANGE, ring_lds + 4u * slot_off + off0, lane, lo0, hi0,
+                                           nullptr);
+                  if (neg0) m = ~m;
+                  if (__ballot(m != 0) != 0)
+                    matched += tile_survivors<STRAT, 32, 1>(q, seg, ring + slot_off, (t - seg_first) * kWTileDocs, m,
+                                                            lane, acc.lds, *acc.ps, la);
+                }
               } else {
                 process_tile_lm<STRAT>(q, seg, pp, t - seg_first, ring + slot_off, ring_lds + 4u * slot_off, lane, acc,
                                        matched, la);
@@ -3031,10 +3076,15 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
               ++t;
             }
           } else {
+            const bool nt = (rl(pp, 6) & kLmStreamNt) != 0;
             while (t < seg_end && ti < issue_end) {
               uint32_t slot_off = (uint32_t)(pslot * img_dw);
-              lm_wait_issue(I, slot_off, R, D, ti - (t + 1), ring_lds + 4u * (uint32_t)(islot * img_dw), ti - ifirst,
-                            16u * (uint32_t)lane);
+              if (nt)
+                lm_wait_issue<true>(I, slot_off, R, D, ti - (t + 1), ring_lds + 4u * (uint32_t)(islot * img_dw),
+                                    ti - ifirst, 16u * (uint32_t)lane);
+              else
+                lm_wait_issue(I, slot_off, R, D, ti - (t + 1), ring_lds + 4u * (uint32_t)(islot * img_dw), ti - ifirst,
+                              16u * (uint32_t)lane);
               ++ti;
               islot = islot + 1 == R ? 0 : islot + 1;
               process_tile_lm<STRAT>(q, seg, pp, t - seg_first, ring + slot_off, ring_lds + 4u * slot_off, lane, acc,

@@ -48,7 +48,21 @@
   X(walk_tab, 1, 0, 1, 0)                                                                                              \
   /* bit set of DevQuery::debug_emit and GdSegPlan::pad (pa_gdense.h): parts of the emit pass / the dense walk        \
      skipped. Keeps the generic kernels: no gdl_jit, and the count + emit passes unless pve_dbg is set */             \
-  X(debug_emit, 0, 0, 127, 1)
+  X(debug_emit, 0, 0, 127, 1)                                                                                          \
+  /* scan_kernel, lane-major: whole tiles of a single equality leaf ask pa_eq_any.h "any match in this lane?" on the  \
+     stream words before the per-doc leaf, 0 / 1 on where legal: columns of up to kEqPrefilterMaxNb bits (default:  \
+     only where the launch also streams nt, the one combination that measured a gain) */                              \
+  X(eq_prefilter, -1, 0, 1, 0)                                                                                         \
+  /* scan_kernel, lane-major hoisted loops: the staged columns' LDS-DMAs carry the nt cache policy, 0 / 1 (default:   \
+     only when one launch stages more bytes than L2 + Infinity Cache hold, so a smaller table that is queried again    \
+     keeps its cache hits) */                                                                                          \
+  X(stream_nt, -1, 0, 1, 0)                                                                                            \
+  /* workgroups of the non-partitioned scan launch (default: one wave per tile up to the resident workgroups). A      \
+     small grid gives every wave several tiles of a small table, so tests reach the hoisted steady-state loops */      \
+  X(scan_grid, -1, 1, 4096, 0)                                                                                         \
+  /* pa_query_reset as one kernel launch instead of memsets + one fill per MIN / MAX / KEYS section, 0 / 1 (default:  \
+     accumulator blocks up to kResetFusedMaxBytes) */                                                                  \
+  X(reset_fused, -1, 0, 1, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;
