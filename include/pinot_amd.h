@@ -40,6 +40,12 @@
  *      aggregate / aggregateGroupBySV / aggregateGroupByMV (every value into a DoubleArrayList) become per-group value
  *      histograms inside the scan, extractAggregationResult / extractGroupByResult the compacted (value id, count)
  *      pairs, extractFinalResult (sort + index at the percentile's rank) a rank select over the bins on the GPU.
+ *  pa_query_set_selection / pa_query_bind_order_remap / pa_query_fetch_selection
+ *      replace, for one segment set on one GPU, operator/query/SelectionOnlyOperator.java,
+ *      operator/query/SelectionOrderByOperator.java:108-112 (the comparator), :139-188 (every ordered expression
+ *      fetched for every matching doc into a bounded priority queue), :193-322 (the rest of the row fetched for the
+ *      rows kept) and operator/combine/SelectionOrderByCombineOperator.java (the segments' queues merged): one fused
+ *      filter + top-K scan over every bound segment, then a select + sort of the candidates and a gather of the cells.
  *  pa_query_accumulators / layout
  *      exposes the device accumulators so the cross-GPU merge of partial aggregates runs as an RCCL
  *      reduce (SUM for COUNT/SUM, MIN, MAX, MAX for HLL registers) — the multi-GPU analogue of
@@ -64,6 +70,9 @@ extern "C" {
 #define PA_MAX_OPS 48
 #define PA_MAX_GROUP_BY 8
 #define PA_MAX_AGGS 16
+#define PA_MAX_ORDER_BY 8         /* ORDER BY columns of a selection */
+#define PA_MAX_SELECT_COLUMNS 64  /* output columns of a selection */
+#define PA_MAX_SELECT_ROWS 65536  /* rows a selection keeps (offset + limit) */
 
 /* error codes */
 #define PA_OK 0
@@ -274,6 +283,64 @@ int pa_query_bind_segment(pa_query* q, int32_t index, const pa_segment* seg,
  * dictId d (int32[segment cardinality]; NULL = identity, the segment's dictionary IS the table-wide one). Call after
  * pa_query_bind_segment, before pa_query_prepare. */
 int pa_query_bind_value_remap(pa_query* q, int32_t index, int32_t agg, const int32_t* remap);
+
+/* ---------------------------------------------------------------- selection queries
+ * SELECT columns ... [WHERE filter] [ORDER BY c1 [DESC], ...] LIMIT [offset,] n. The query is created from an
+ * aggregation-only spec (its filter is the selection's; its aggregations are ignored, e.g. one COUNT) and turned into
+ * a selection before any segment is bound. The result is the num_rows smallest matching docs of all bound segments
+ * under the ORDER BY comparator (SelectionOrderByOperator.java:108-112), ties broken by (segment bind index, docId)
+ * ascending; without ORDER BY the first num_rows matching docs in that order (SelectionOnlyOperator.java).
+ *
+ * Sort key: one unsigned 64-bit word, the ORDER BY components most significant first. A dictionary column contributes
+ * its table-wide value id (ceil(log2(cardinality)) bits; 0 bits for a dictionary of one value) through a per-segment
+ * remap, so ids must follow the order of the values (STRING: String.compareTo, i.e. UTF-16 code units). A raw INT /
+ * LONG column contributes the value with its sign bit flipped (32 / 64 bits), a raw FLOAT / DOUBLE column the
+ * total-order image of the value with every NaN made the canonical one first (Double.compare: -0.0 < 0.0, NaN
+ * greatest). A descending component is complemented inside its width. pa_query_prepare fails with PA_EUNSUPPORTED for
+ * components wider than 64 bits together, for multi-value or BYTES columns, and for a column that is
+ * dictionary-encoded in some bound segments only. */
+typedef struct {
+  int32_t num_order_by;
+  int32_t order_by_columns[PA_MAX_ORDER_BY];
+  int32_t order_by_desc[PA_MAX_ORDER_BY];          /* 1 = descending */
+  int64_t order_by_cardinality[PA_MAX_ORDER_BY];   /* size of the column's table-wide dictionary; 0 = a raw column,
+                                                      ordered by value */
+  int32_t num_columns;
+  int32_t columns[PA_MAX_SELECT_COLUMNS];          /* output columns (pa_query_fetch_selection's out_cells order) */
+  int32_t num_rows;                                /* offset + limit (SelectionOrderByOperator._numRowsToKeep),
+                                                      1..PA_MAX_SELECT_ROWS, else PA_EUNSUPPORTED */
+} pa_select_spec;
+
+/* Before pa_query_bind_segment and pa_query_prepare. pa_query_execute / reset / scan then drive the selection's scan;
+ * pa_query_fetch fails on such a query (pa_query_fetch_selection reads it); pa_query_matched_docs, the leaf bitmaps
+ * and pa_query_execution_stats work as for an aggregation. */
+int pa_query_set_selection(pa_query* q, const pa_select_spec* spec);
+
+/* remap[d] = the table-wide value id of dictId d of ORDER BY column `order_by_index` in the segment bound at
+ * `segment_index` (int32[segment cardinality], every id < order_by_cardinality; NULL = identity): the role
+ * pa_query_bind_segment's group_remaps play for GROUP BY. After pa_query_bind_segment, before pa_query_prepare. */
+int pa_query_bind_order_remap(pa_query* q, int32_t segment_index, int32_t order_by_index, const int32_t* remap);
+
+/* The result of the last scan: min(num_rows, matched docs) rows in ascending (key, segment, doc) order; row r is doc
+ * out_docs[r] of the segment bound at out_segments[r] with sort key out_keys[r] (each array holds `capacity` elements;
+ * any may be NULL). out_cells[c] (int64[capacity], may be NULL) takes output column c of every row: the segment's
+ * dictId for a dictionary column (the host decodes it through that segment's dictionary, as
+ * SelectionOperatorUtils.getRowsFromBlock does through the block's value sets), the value of a raw INT / LONG column,
+ * the bits of the value as a double for a raw FLOAT / DOUBLE column. Returns the number of rows (may exceed capacity:
+ * then only `capacity` were written), <0 on error; capacity = 0 only counts. Replaces the queue drain of
+ * SelectionOrderByOperator.java:193-322 and SelectionOrderByCombineOperator's merge. Synchronises `stream`. */
+int64_t pa_query_fetch_selection(pa_query* q, void* stream, int64_t capacity, int32_t* out_segments, int32_t* out_docs,
+                                 uint64_t* out_keys, int64_t* const* out_cells);
+
+/* Docs of every bound segment that passed the filter in the scan the last pa_query_fetch_selection read
+ * (int64[num_segments]): SelectionOrderByOperator's per-segment numDocsScanned, which its numEntriesScannedPostFilter
+ * needs (SelectionOrderByOperator.java:175,239,300). */
+int pa_query_selection_segment_docs(const pa_query* q, int64_t* out);
+
+/* Counters of that scan, for tests and measurement: out[0] = candidates the scan waves appended, out[1] = in-place
+ * compactions they ran (a wave's candidate segment filled), out[2] = scan waves launched, out[3] = candidates per wave
+ * (CAP). */
+int pa_query_selection_counters(const pa_query* q, int64_t* out);
 
 /* Tests and measurement only: overrides one planner decision of this query (the tunings, their ranges and defaults:
  * pinot_amd/csrc/pa_tuning.h; the library reads none of them from the environment). Before pa_query_prepare.

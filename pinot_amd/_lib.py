@@ -12,6 +12,9 @@ PA_MAX_LEAVES = 16
 PA_MAX_OPS = 48
 PA_MAX_GROUP_BY = 8
 PA_MAX_AGGS = 16
+PA_MAX_ORDER_BY = 8
+PA_MAX_SELECT_COLUMNS = 64
+PA_MAX_SELECT_ROWS = 65536
 
 PA_INT, PA_LONG, PA_FLOAT, PA_DOUBLE, PA_STRING, PA_BYTES = range(6)
 PA_LEAF_DICT_RANGE, PA_LEAF_DICT_SET, PA_LEAF_RAW_RANGE, PA_LEAF_MV_DICT_RANGE, PA_LEAF_MV_DICT_SET, PA_LEAF_RAW_SET = range(6)
@@ -61,6 +64,8 @@ EXPORTED = [
     "pa_segment_add_raw_column", "pa_segment_num_docs", "pa_segment_device_bytes", "pa_segment_destroy",
     "pa_query_create", "pa_query_set_tuning", "pa_query_results_invalid", "pa_query_bind_segment",
     "pa_query_bind_value_remap", "pa_query_prepare", "pa_query_num_keys",
+    "pa_query_set_selection", "pa_query_bind_order_remap", "pa_query_fetch_selection",
+    "pa_query_selection_segment_docs", "pa_query_selection_counters",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
     "pa_query_partition_keys",
@@ -109,6 +114,18 @@ class QuerySpec(ctypes.Structure):
     ]
 
 
+class SelectSpec(ctypes.Structure):
+    _fields_ = [
+        ("num_order_by", ctypes.c_int32),
+        ("order_by_columns", ctypes.c_int32 * PA_MAX_ORDER_BY),
+        ("order_by_desc", ctypes.c_int32 * PA_MAX_ORDER_BY),
+        ("order_by_cardinality", ctypes.c_int64 * PA_MAX_ORDER_BY),
+        ("num_columns", ctypes.c_int32),
+        ("columns", ctypes.c_int32 * PA_MAX_SELECT_COLUMNS),
+        ("num_rows", ctypes.c_int32),
+    ]
+
+
 class LeafParams(ctypes.Structure):
     _fields_ = [
         ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("negate", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -143,6 +160,11 @@ def _declare(lib):
         "pa_query_results_invalid": (i32, [vp]),
         "pa_query_bind_segment": (ctypes.c_int, [vp, i32, vp, ctypes.POINTER(LeafParams), vp]),
         "pa_query_bind_value_remap": (ctypes.c_int, [vp, i32, i32, vp]),
+        "pa_query_set_selection": (ctypes.c_int, [vp, ctypes.POINTER(SelectSpec)]),
+        "pa_query_bind_order_remap": (ctypes.c_int, [vp, i32, i32, vp]),
+        "pa_query_fetch_selection": (i64, [vp, vp, i64, vp, vp, vp, vp]),
+        "pa_query_selection_segment_docs": (ctypes.c_int, [vp, vp]),
+        "pa_query_selection_counters": (ctypes.c_int, [vp, vp]),
         "pa_query_prepare": (ctypes.c_int, [vp]),
         "pa_query_num_keys": (i64, [vp]),
         "pa_query_execute": (ctypes.c_int, [vp, vp]),

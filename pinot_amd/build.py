@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpinot_amd.so")
 SOURCES = ["pa_scan_part_a.hip", "pa_scan_part_b.hip", "pa_scan_part_mv.hip", "pa_scan_std.hip", "pa_scan_lane.hip",
-           "pa_scan_gdense.hip", "pa_kernels.hip", "pa_merge.hip", "pa_stats.hip", "pa_pve.hip", "pa_segment.hip",
+           "pa_scan_gdense.hip", "pa_scan_select.hip", "pa_select.hip", "pa_kernels.hip", "pa_merge.hip", "pa_stats.hip", "pa_pve.hip", "pa_segment.hip",
            "pa_plan.hip", "pa_plan_kernels.hip", "pa_jit.hip", "pa_capi.hip", "pa_fetch.hip", "pa_hist.hip",
            "pa_stats_host.hip"]
 # every header under csrc/ (globbed, so a new one is covered without an edit here) and the public C-ABI header

@@ -115,7 +115,8 @@ int pa_query_prepare(pa_query* q) {
     if (!q->segs[i]) return fail(PA_EINVAL, "segment " + std::to_string(i) + " not bound");
   Prep P;
   std::memset(&q->hq, 0, sizeof(q->hq));
-  int rc = plan_filter(q, P);
+  int rc = q->is_select ? select_validate(q) : PA_OK;
+  if (!rc) rc = plan_filter(q, P);
   if (!rc) rc = plan_slots(q, P);
   if (!rc) rc = plan_key_space(q, P);
   if (!rc) rc = plan_limit(q, P);
@@ -158,6 +159,10 @@ int pa_query_prepare(pa_query* q) {
   const int64_t want = (total_tiles + wpw - 1) / wpw;
   q->grid = (int)std::max<int64_t>(1, std::min(max_wg, want));
   if (q->tune.scan_grid > 0 && !q->partitioned) q->grid = (int)std::min<int64_t>(q->grid, q->tune.scan_grid);
+  if (q->is_select) {  // (may shrink the grid: every wave owns a candidate segment of the scratch block)
+    rc = select_plan(q);
+    if (rc) return rc;
+  }
 
   if (q->partitioned) {
     // the count pass: the same tiles, waves and grid; only the group-by and filter columns staged
@@ -222,6 +227,8 @@ int pa_query_reset(pa_query* q, void* stream) {
   if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
   hipStream_t st = (hipStream_t)stream;
   char* block = (char*)(q->external_acc ? q->external_acc : q->acc.p);
+  if (q->is_select)
+    if (int rc = select_reset(q, st)) return rc;
   // Small blocks (the common case): one launch writes zeros and identities (the block is whole 256-byte units). Larger
   // ones keep the memsets, whose rate matters there and whose extra launches no longer do.
   auto identity = [](const Section& sc, int64_t& v) {

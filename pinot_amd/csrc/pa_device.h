@@ -53,7 +53,10 @@ enum Strategy : int32_t {
   // the count pass of a query grouping by a multi-value column (one record per (doc, value) pair)
   STRAT_PCOUNT_MV = 13,
   // STRAT_GDENSE over the LDS-DMA ring with the lane-major walk (gdl_tile): 8- / 16-wave workgroups
-  STRAT_GDENSE_LM8 = 14, STRAT_GDENSE_LM16 = 15
+  STRAT_GDENSE_LM8 = 14, STRAT_GDENSE_LM16 = 15,
+  // selection (SELECT columns ... ORDER BY ... LIMIT): filter + per-wave top-K candidates (pa_scan.h "selection");
+  // its code lies above the emit variants' range (is_pemit)
+  STRAT_SELECT = 128
 };
 __host__ __device__ constexpr bool is_pcount(int s) { return s == STRAT_PCOUNT || s == STRAT_PCOUNT_MV; }
 // STRAT_GDENSE: 4-wave workgroups; STRAT_GDENSE8 / STRAT_GDENSE12: the same kernel with 8- / 12-wave workgroups (2 / 3
@@ -107,7 +110,7 @@ constexpr int kEmitBigWaves = 16;
 __host__ __device__ constexpr int pemit_strat(int vf, int hh, int big = 0, int mv = 0) {
   return kPemitBase + 2 * (vf + 1) + (hh ? 1 : 0) + (big ? 16 : 0) + (mv ? 32 : 0);
 }
-__host__ __device__ constexpr bool is_pemit(int s) { return s >= kPemitBase; }
+__host__ __device__ constexpr bool is_pemit(int s) { return s >= kPemitBase && s < STRAT_SELECT; }
 __host__ __device__ constexpr int pemit_vf(int s) { return (((s - kPemitBase) & 15) >> 1) - 1; }
 __host__ __device__ constexpr bool pemit_hh(int s) { return ((s - kPemitBase) & 1) != 0; }
 __host__ __device__ constexpr int pemit_big(int s) { return ((s - kPemitBase) >> 4) & 1; }
@@ -322,7 +325,52 @@ struct DevQuery {
   unsigned long long* leap_out;  // (layout: pa_scan.h "fused execution statistics")
   int64_t leap_cap;              // list entries per scan wave (E docs)
   int64_t leap_slices;           // scan waves (grid x waves per workgroup): one list slice each
+  const struct SelDesc* sel;     // STRAT_SELECT: the selection's descriptor (nullptr otherwise)
 };
+// ---------------------------------------------------------------- selection (STRAT_SELECT)
+// One candidate of the top-K: (key, row) compared as one 128-bit unsigned number. key = the ORDER BY components,
+// most significant first, each in its own bit field (SelPart); row = segment bind index << 32 | docId (the tie-break).
+struct alignas(16) SelEnt {
+  uint64_t key, row;
+};
+// One column of one segment as the selection reads it (order-by component or output cell).
+struct SelCol {
+  const uint32_t* words;     // SV dict: stream words (past the guard words)
+  const void* raw;           // SV raw: values
+  const int32_t* remap;      // order-by: dictId -> table-wide value id (nullptr = identity)
+  int32_t kind;              // COL_SV_DICT / COL_SV_RAW
+  int32_t nbits;
+  int32_t vtype;
+  int32_t lds_off;           // order-by dictionary column the filter stages: its region in the tile image, else -1
+};
+struct SelPart {
+  int32_t width;             // bits of the component (0: a dictionary of one value)
+  int32_t shift;             // its position in the key
+  int32_t desc;              // 1: complemented inside its width
+  int32_t pad;
+};
+constexpr int kSelLdsWords = 272;   // LDS words of one radix-select state: 256 digit counts + the chosen digit and rank
+struct SelDesc {
+  int32_t nob, nout;
+  int32_t K;                 // rows to keep (offset + limit)
+  int32_t cap;               // candidates per scan wave (> K)
+  int32_t key_bits, row_bits;  // bits in use of SelEnt::key / SelEnt::row (the select's digit passes skip the rest)
+  int32_t nseg, waves;       // bound segments, scan waves of the launch
+  SelPart part[PA_MAX_ORDER_BY];
+  const SelCol* ob_cols;     // [nseg][nob]
+  const SelCol* out_cols;    // [nseg][nout]
+  SelEnt* scratch;           // [waves][cap]: every scan wave's candidates
+  uint32_t* wave_n;          // [waves]: candidates each wave left
+  unsigned long long* bound; // the smallest K-th key any wave has published (all ones: none yet)
+  unsigned long long* cursor;   // finish: candidates gathered
+  unsigned long long* counters; // [0] candidates appended, [1] compactions
+  unsigned long long* seg_docs; // [nseg]: docs of each segment that passed the filter
+  SelEnt* cand;              // finish: the gathered candidates [waves * cap]
+  SelEnt* sorted;            // finish: the result, ascending [next power of two >= K]
+  int64_t* cells;            // finish: [nout][K] output cells
+  uint32_t* result_n;        // finish: rows of the result
+};
+
 // STRAT_GDENSE per-segment parameter table: 64 dwords, loaded once per segment into ONE VGPR (lane k holds dword k)
 // and read back with v_readlane at compile-time lanes, so the doc loop never issues a scalar load (an SMEM wait is an
 // lgkmcnt wait, which also waits for every LDS operation in flight).

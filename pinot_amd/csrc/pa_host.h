@@ -312,8 +312,24 @@ struct pa_query {
   void* external_acc = nullptr;
   std::vector<Section> sections;
   std::vector<int> agg_section;  // agg -> section index (-1 for COUNT)
+  // selection (pa_query_set_selection; pa_select.hip): the spec, the order-by remaps [seg][order-by] (empty =
+  // identity), the descriptor the scan and the finish kernels read, and their buffers (sel_hdr: bound, cursor,
+  // counters, per-segment docs, result rows, then every wave's candidate count)
+  bool is_select = false;
+  pa_select_spec sel_spec{};
+  std::vector<std::vector<std::vector<int32_t>>> sel_remaps;
+  SelDesc hsel{};
+  DevBuf sel_desc, sel_hdr, sel_scratch, sel_cand, sel_sorted, sel_cells;
+  std::vector<int64_t> sel_seg_docs;  // read by the last pa_query_fetch_selection
+  int64_t sel_counters[4] = {0, 0, 0, 0};
 
   ~pa_query() {
+    dev_free(sel_desc);
+    dev_free(sel_hdr);
+    dev_free(sel_scratch);
+    dev_free(sel_cand);
+    dev_free(sel_sorted);
+    dev_free(sel_cells);
     dev_free(dq);
     dev_free(dsegs);
     dev_free(dplans);
@@ -428,6 +444,10 @@ PartScratch scratch_of(const pa_query* q, void* base);
 size_t leap_header_bytes(const pa_query* q);
 int plan_leaps(pa_query* q, const Prep& P);
 int alloc_leaps(pa_query* q, const Prep& P);
+// pa_select.hip
+int select_validate(pa_query* q);               // prepare: the selection's columns and key against the bound segments
+int select_plan(pa_query* q);                   // prepare, once the grid is known: caps it, allocates, fills hq.sel
+int select_reset(pa_query* q, hipStream_t st);  // pa_query_reset
 // pa_jit.hip
 int jit_plan(pa_query* q, const Prep& P, int cus);
 void jit_fill_pointers(pa_query* q, JitArgs& a);

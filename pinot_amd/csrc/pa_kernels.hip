@@ -1996,6 +1996,7 @@ hipError_t launch_leap_search(const DevQuery* q, const DevSeg* segs, int64_t sli
 static const void* scan_fn(int strategy, int steps, int lm) {
   if (const void* f = scan_fn_std(strategy, steps, lm)) return f;
   if (const void* f = scan_fn_gdense(strategy, lm)) return f;
+  if (const void* f = scan_fn_select(strategy, steps)) return f;
   if (const void* f = scan_fn_part_a(strategy)) return f;
   if (const void* f = scan_fn_part_mv(strategy)) return f;
   return scan_fn_part_b(strategy);

@@ -446,6 +446,20 @@ bool plan_partitions(pa_query* q, Prep& P, TilePlan& emit_plan, TilePlan& count_
 int plan_kernels(pa_query* q, Prep& P, TilePlan& plan, TilePlan& count_plan) {
   const pa_query_spec& s = q->spec;
   const int64_t K = q->num_keys;
+  if (q->is_select) {
+    // Selection: the step-major scan with the top-K candidate strategy; in front of the tile rings every wave's radix
+    // select state (digit counts). The spec's aggregations are not computed.
+    q->strategy = STRAT_SELECT;
+    q->partitioned = false;
+    P.lds_acc = (size_t)kWavesPerWG * kSelLdsWords * 4;
+    plan = plan_tiles(q, q->hsegs, STRAT_SELECT, false, P.lds_acc, false);
+    if (plan.score < 0) return fail(PA_EUNSUPPORTED, "staged columns too wide for the LDS tile ring");
+    P.lm = false;
+    q->lds_bytes = (int)plan.lds;
+    q->steps = plan.steps;
+    q->dma_slots = plan.dma;
+    return PA_OK;
+  }
   // Lane-major kernel: every eager literal is a dictionary leaf on a staged column and the per-segment plan table
   // has room for the staged columns and eager literals (otherwise the step-major kernel runs the query).
   bool lm = !(s.flags & (PA_QF_NO_LANE_MAJOR | PA_QF_STEPS16)) && q->num_eager <= kLmEager;
@@ -771,7 +785,7 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
   for (int li = 0; li < PA_MAX_LEAVES; ++li) h.gd_lut[li] = -1;
   h.xcd_major = (P.dense || is_gdense(q->strategy)) ? 1 : 0;
   h.lds_count_off = 0;
-  h.lds_acc_bytes = (q->strategy == STRAT_LDS || is_gdense(q->strategy) || is_lane(q->strategy))
+  h.lds_acc_bytes = (q->strategy == STRAT_LDS || is_gdense(q->strategy) || is_lane(q->strategy) || q->strategy == STRAT_SELECT)
                         ? (uint32_t)P.lds_acc : 0;
   if (is_gdense(q->strategy)) {
     // per-segment parameter tables (GdSegPlan): the query's key box and LDS layout + the segment's staged regions

@@ -62,7 +62,13 @@
   X(scan_grid, -1, 1, 4096, 0)                                                                                         \
   /* pa_query_reset as one kernel launch instead of memsets + one fill per MIN / MAX / KEYS section, 0 / 1 (default:  \
      accumulator blocks up to kResetFusedMaxBytes) */                                                                  \
-  X(reset_fused, -1, 0, 1, 0)
+  X(reset_fused, -1, 0, 1, 0)                                                                                          \
+  /* selection (STRAT_SELECT): bound in MiB of the scan waves' candidate block (waves x CAP x 16 bytes); the launch's \
+     grid shrinks until the block fits. The default of 256 is NOT measured: it is one Infinity Cache's worth */       \
+  X(select_scratch_mib, 256, 1, 16384, 0)                                                                              \
+  /* selection: candidates per scan wave (CAP), K + 1 .. max(2 K, 128) (checked at prepare; default: that maximum).    \
+     A small CAP makes small tables reach the in-place compaction */                                                  \
+  X(select_cap, -1, 2, 131072, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;

@@ -482,6 +482,7 @@ class GpuQueryExecutor:
         for name, value in self.tuning.items():
             L.check(lib.pa_query_set_tuning(self.handle, name.encode(), int(value)), "pa_query_set_tuning")
         self._keep = []
+        self._after_create()
         for si, (g, params) in enumerate(zip(self.gsegs, per_seg)):
             arr = (L.LeafParams * max(1, len(params)))()
             for li, p in enumerate(params):
@@ -520,6 +521,7 @@ class GpuQueryExecutor:
                 rm = np.searchsorted(vd, d).astype(np.int32)
                 self._keep.append(rm)
                 L.check(lib.pa_query_bind_value_remap(self.handle, si, i, rm.ctypes.data), "pa_query_bind_value_remap")
+        self._before_prepare()
         L.check(lib.pa_query_prepare(self.handle), "pa_query_prepare")
         self.num_keys = int(lib.pa_query_num_keys(self.handle))
         hashed, shifts = ctypes.c_int32(), (ctypes.c_int32 * max(1, len(q.group_by)))()
@@ -532,6 +534,12 @@ class GpuQueryExecutor:
         for gd in self.global_dicts:
             self.strides.append(s)
             s *= len(gd) if gd is not None else 1
+
+    def _after_create(self):
+        """Between pa_query_create and the first pa_query_bind_segment (SelectionExecutor sets the selection here)."""
+
+    def _before_prepare(self):
+        """After every segment is bound, before pa_query_prepare (SelectionExecutor binds its order remaps here)."""
 
     # ------------------------------------------------------------------ execution
     def execute(self, stream=None):
@@ -576,7 +584,7 @@ class GpuQueryExecutor:
         code = out["plan"]["strategy"]
         out["plan"]["strategy"] = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane", 6: "lane", 7: "lane",
                                     8: "lds_dense", 9: "lds_dense", 10: "lds_dense", 11: "lds_dense", 12: "lds_dense",
-                                    14: "lds_dense", 15: "lds_dense"}[code]
+                                    14: "lds_dense", 15: "lds_dense", 128: "select"}[code]
         out["plan"]["variant"] = STRATEGY_VARIANTS.get(code, str(code))
         out["plan"]["eager_literals"] = int(L.lib().pa_query_num_eager_literals(self.handle))
         out["plan"]["lane_major"] = int(L.lib().pa_query_lane_major(self.handle))
@@ -895,7 +903,170 @@ class GpuQueryExecutor:
 # the kernel variant behind each pa_query_plan strategy code (pa_device.h Strategy)
 STRATEGY_VARIANTS = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane_cnt", 6: "lane_raw", 7: "lane_dict",
                      8: "gdense4", 9: "gdense8", 10: "gdense12", 11: "gdense_rs12", 12: "gdense_rs8", 14: "gdense_lm8",
-                     15: "gdense_lm16"}
+                     15: "gdense_lm16", 128: "select"}
+
+
+class SelectionExecutor(GpuQueryExecutor):
+    """SELECT columns | * ... [WHERE ...] [ORDER BY c1 [DESC], ...] LIMIT [offset,] n over the segments of one GPU:
+    SelectionOnlyOperator / SelectionOrderByOperator on every segment + SelectionOrderByCombineOperator, as one fused
+    filter + top-K scan (include/pinot_amd.h "selection queries"). The server keeps K = offset + limit rows
+    (SelectionOrderByOperator._numRowsToKeep); reduce.merge_selection applies the offset.
+
+    table_dicts: optional {ORDER BY column: values ascending in the column's order (selection.table_order_dictionary)}
+    — the table-wide dictionary whose ranks the sort keys hold; ranks of different servers agree only when they share
+    it. By default the union of these segments' dictionaries."""
+
+    def __init__(self, query: Q.Query, gpu_segments: List[GpuSegment], flags=0, table_dicts=None, tuning=None):
+        from . import selection as S
+        if not query.is_selection:
+            raise ValueError("not a selection query")
+        if not gpu_segments:
+            raise ValueError("no segments")
+        if str(query.options.get("enableNullHandling", "false")).lower() == "true":
+            raise UnsupportedQuery("selection with null handling")
+        self.selection = query
+        self.num_rows = int(query.offset) + int(query.limit)
+        if self.num_rows > L.PA_MAX_SELECT_ROWS:
+            raise UnsupportedQuery("selection keeps %d rows (offset + limit), more than PA_MAX_SELECT_ROWS (%d)"
+                                   % (self.num_rows, L.PA_MAX_SELECT_ROWS))
+        seg0 = gpu_segments[0].segment
+        for o in query.order_by:
+            if not isinstance(o.expr, str) or o.expr not in seg0.columns:
+                raise UnsupportedQuery("selection ordered by a transform expression: %r" % (o.expr,))
+        for c in query.select_columns:
+            if c not in seg0.columns:
+                raise UnsupportedQuery("transform expression or unknown column in the select list: %r" % (c,))
+        if len(query.order_by) > L.PA_MAX_ORDER_BY:
+            raise UnsupportedQuery("too many order-by columns")
+        self.result_columns = S.result_columns(query, seg0.columns)
+        if len(self.result_columns) > L.PA_MAX_SELECT_COLUMNS:
+            raise UnsupportedQuery("too many select columns")
+        for c in self.result_columns:
+            if not seg0.column(c).single_value:
+                raise UnsupportedQuery("multi-value column %s in a selection" % c)
+        self.result_types = [seg0.column(c).data_type for c in self.result_columns]
+        self.order_columns = []
+        for o in query.order_by:
+            if o.expr not in [c for c, _ in self.order_columns]:
+                self.order_columns.append((o.expr, bool(o.asc)))
+        self.order_dicts = dict(table_dicts or {})
+        self.total_docs = sum(g.segment.num_docs for g in gpu_segments)
+        # the reference runs SelectionOrderByOperator (a full scan whose statistics are modelled) only when the first
+        # ORDER BY column is not sorted in the segment; otherwise, and without ORDER BY, it stops early
+        bound = [g.segment for g in gpu_segments if g.segment.num_docs > 0]
+        self.stats_modelled = bool(self.order_columns) and not any(
+            s.column(self.order_columns[0][0]).is_sorted for s in bound)
+        self.bound_index = [i for i, g in enumerate(gpu_segments) if g.segment.num_docs > 0]
+        count = dataclasses.replace(query, aggregations=[Q.Aggregation("COUNT")], aliases=[None], order_by=[],
+                                    select_columns=[], num_select_aggs=1, select_star=False, limit=10, offset=0)
+        if self.num_rows == 0 or not bound:  # EmptySelectionOperator / nothing to scan: no plan, no launch
+            self.query, self.handle, self.placeholder, self.segs, self.gsegs = count, None, None, [], []
+            self.all_segs = [g.segment for g in gpu_segments]
+            self.match_none = False
+            return
+        try:
+            super().__init__(count, gpu_segments, flags=flags, tuning=tuning)
+        except L.PinotAmdError as e:
+            if "(%d)" % -4 in str(e) and not isinstance(e, UnsupportedQuery):  # PA_EUNSUPPORTED
+                raise UnsupportedQuery(str(e))
+            raise
+
+    def _after_create(self):
+        from . import selection as S
+        ids = self.gsegs[0].column_ids
+        spec = L.SelectSpec()
+        spec.num_order_by = len(self.order_columns)
+        self.order_remaps = []  # [order-by][segment] -> int32 ranks, or None for identity / a raw column
+        for j, (name, asc) in enumerate(self.order_columns):
+            cols = [s.column(name) for s in self.segs]
+            spec.order_by_columns[j] = ids[name]
+            spec.order_by_desc[j] = 0 if asc else 1
+            if not any(c.has_dictionary for c in cols):
+                spec.order_by_cardinality[j] = 0  # raw: ordered by value
+                self.order_remaps.append([None] * len(cols))
+                continue
+            if not all(c.has_dictionary for c in cols):
+                raise UnsupportedQuery("order-by column %s is dictionary-encoded in some segments only" % name)
+            dt = cols[0].data_type
+            if name in self.order_dicts:
+                keys = S.order_keys(self.order_dicts[name], dt)
+            else:
+                _, keys = S.table_order_dictionary([c.dictionary for c in cols], dt)
+            spec.order_by_cardinality[j] = len(keys)
+            rms = []
+            for c in cols:
+                rm = S.order_remap(keys, c.dictionary, dt)
+                rms.append(None if len(rm) == len(keys) and np.array_equal(rm, np.arange(len(keys))) else rm)
+            self.order_remaps.append(rms)
+        spec.num_columns = len(self.result_columns)
+        for c, name in enumerate(self.result_columns):
+            spec.columns[c] = ids[name]
+        spec.num_rows = self.num_rows
+        L.check(L.lib().pa_query_set_selection(self.handle, ctypes.byref(spec)), "pa_query_set_selection")
+
+    def _before_prepare(self):
+        for j, rms in enumerate(self.order_remaps):
+            for si, rm in enumerate(rms):
+                if rm is not None:
+                    self._keep.append(rm)
+                    L.check(L.lib().pa_query_bind_order_remap(self.handle, si, j, rm.ctypes.data),
+                            "pa_query_bind_order_remap")
+
+    def counters(self):
+        """{candidates appended, compactions, scan waves, CAP} of the scan the last fetch read."""
+        out = np.zeros(4, dtype=np.int64)
+        L.check(L.lib().pa_query_selection_counters(self.handle, out.ctypes.data), "pa_query_selection_counters")
+        return dict(zip(("appended", "compactions", "waves", "cap"), out.tolist()))
+
+    def fetch(self, stream=None, execution_stats=True):
+        """The SelectionResult of the last scan (synchronises `stream`)."""
+        from . import selection as S
+        res = S.SelectionResult(list(self.result_columns), list(self.result_types), num_total_docs=self.total_docs)
+        if self.handle is None:  # LIMIT 0 (EmptySelectionOperator: statistics 0, 0, 0) or no docs at all
+            res.num_docs_scanned = res.num_entries_scanned_in_filter = res.num_entries_scanned_post_filter = 0
+            return res
+        lib = L.lib()
+        K, nout = self.num_rows, len(self.result_columns)
+        segs, docs = np.zeros(K, dtype=np.int32), np.zeros(K, dtype=np.int32)
+        keys = np.zeros(K, dtype=np.uint64)
+        cells = np.zeros((max(nout, 1), K), dtype=np.int64)
+        ptrs = (ctypes.c_void_p * max(nout, 1))(*[cells[c].ctypes.data for c in range(max(nout, 1))])
+        n = L.check(lib.pa_query_fetch_selection(self.handle, stream, K, segs.ctypes.data, docs.ctypes.data,
+                                                 keys.ctypes.data, ptrs), "pa_query_fetch_selection")
+        segs, docs, keys = segs[:n], docs[:n], keys[:n]
+        cols = []
+        for c, name in enumerate(self.result_columns):
+            out = np.empty(n, dtype=object)
+            for si in np.unique(segs).tolist():
+                m = segs == si
+                col = self.segs[si].column(name)
+                cell = cells[c, :n][m]
+                if col.has_dictionary:
+                    vals = col.dictionary[cell]
+                elif col.data_type in ("FLOAT", "DOUBLE"):
+                    vals = cell.view(np.float64).astype(np.float32 if col.data_type == "FLOAT" else np.float64)
+                else:
+                    vals = cell.astype(np.int32 if col.data_type == "INT" else np.int64)
+                out[m] = vals.tolist()
+            cols.append(out.tolist())
+        res.rows = [list(r) for r in zip(*cols)] if cols else [[] for _ in range(n)]
+        res.segments = np.asarray([self.bound_index[s] for s in segs.tolist()], dtype=np.int32)
+        res.docs, res.keys = docs.copy(), keys.copy()
+        if self.stats_modelled:
+            matched = int(lib.pa_query_matched_docs(self.handle))
+            res.num_docs_scanned = matched
+            per = np.zeros(len(self.segs), dtype=np.int64)
+            L.check(lib.pa_query_selection_segment_docs(self.handle, per.ctypes.data), "pa_query_selection_segment_docs")
+            res.num_entries_scanned_post_filter = S.post_filter_entries(
+                per.tolist(), K, len(self.order_columns), nout - len(self.order_columns))
+            if execution_stats:
+                res.num_entries_scanned_in_filter = self.execution_stats(stream, matched)[0]
+        return res
+
+    def run(self, stream=None):
+        if self.handle is not None:
+            self.execute(stream)
+        return self.fetch(stream)
 
 
 def _has_comparison(f):

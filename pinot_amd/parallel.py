@@ -554,3 +554,14 @@ class DistributedAccumulators:
             return True
         self.reduce(dst=dst, execution_stats=execution_stats, group=group)
         return False
+
+
+def gather_selection(result, query, group=None):
+    """Every rank's SelectionResult (engine.SelectionExecutor.fetch) to every rank, merged as the broker merges servers
+    (reduce.merge_selection, rank order = server order). The rows are few (at most offset + limit per rank), so they
+    travel as objects: no collective kernel. Returns (column names, rows), the same on every rank."""
+    from .reduce import merge_selection
+    world = dist.get_world_size(group)
+    parts = [None] * world
+    dist.all_gather_object(parts, result, group=group)
+    return merge_selection(parts, query)

@@ -3,6 +3,8 @@ parser for the SQL subset the reference's query tests use on this path:
 
   SELECT agg(col) [AS alias], ... FROM t [WHERE filter] [GROUP BY c1, ...] [ORDER BY x [ASC|DESC], ...]
   [LIMIT n] [OPTION(k=v, ...)]
+  SELECT col, ... | * FROM t [WHERE filter] [ORDER BY c1 [ASC|DESC], ...] [LIMIT [offset,] n | LIMIT n OFFSET m]
+  (a selection: Query.is_selection; SelectionOnlyOperator / SelectionOrderByOperator on the server)
 
 filter: AND / OR / NOT / ( ) over  col = v | col != v | col <> v | col < v | col <= v | col > v | col >= v |
         col BETWEEN a AND b | col IN (...) | col NOT IN (...) | REGEXP_LIKE(col, 'regex') | col [NOT] LIKE 'pattern'
@@ -221,6 +223,13 @@ class Query:
     options: dict = field(default_factory=dict)
     select_columns: List[str] = field(default_factory=list)
     num_select_aggs: int = -1   # aggregations after this index are ORDER BY-only
+    offset: int = 0             # LIMIT offset, n / LIMIT n OFFSET offset (selections: the broker drops these rows)
+    select_star: bool = False   # SELECT *: every physical column of the schema
+
+    @property
+    def is_selection(self):
+        """No aggregation and no GROUP BY: SELECT columns / * [ORDER BY ...] (QueryContextUtils.isSelectionQuery)."""
+        return not self.aggregations and not self.group_by
 
     @property
     def num_groups_limit(self):
@@ -235,6 +244,9 @@ class Query:
         for a in self.aggregations:
             if a.column:
                 cols.add(a.column)
+        if self.is_selection:
+            cols.update(self.select_columns)
+            cols.update(o.expr for o in self.order_by if isinstance(o.expr, str))
 
         def walk(f):
             if f is None:
@@ -453,9 +465,12 @@ class _Parser:
     def parse(self):
         self.expect_kw("SELECT")
         aggs, aliases, plain_cols = [], [], []
+        star = False
         while True:
             tok, nxt = self.peek(), self.peek(1)
-            if tok[0] == "id" and not (nxt[0] == "op" and nxt[1] == "("):
+            if self.op("*"):
+                star = True
+            elif tok[0] == "id" and not (nxt[0] == "op" and nxt[1] == "("):
                 plain_cols.append(self.ident())  # group-by column in the select list
             else:
                 aggs.append(self.aggregation())
@@ -467,6 +482,9 @@ class _Parser:
         q = Query(aggregations=aggs, aliases=aliases)
         q.select_columns = plain_cols
         q.num_select_aggs = len(aggs)
+        q.select_star = star
+        if star and aggs:
+            raise ValueError("SELECT * next to aggregations")
         if self.kw("WHERE"):
             q.filter = self.filter_or()
         if self.kw("GROUP"):
@@ -499,6 +517,12 @@ class _Parser:
                     break
         if self.kw("LIMIT"):
             q.limit = int(self.literal())
+            if self.op(","):  # LIMIT offset, n
+                q.offset, q.limit = q.limit, int(self.literal())
+            elif self.kw("OFFSET"):
+                q.offset = int(self.literal())
+            if q.limit < 0 or q.offset < 0:
+                raise ValueError("negative LIMIT / OFFSET")
         if self.kw("TOP"):
             q.limit = int(self.literal())
         if self.kw("OPTION"):
@@ -514,6 +538,9 @@ class _Parser:
             self.expect_op(")")
         if self.peek()[0] is not None:
             raise ValueError("trailing tokens: %r" % (self.t[self.i:],))
+        if aggs and (plain_cols or star) and not q.group_by:
+            # (the reference: "... should appear in GROUP BY clause", CalciteSqlParser.validateGroupByClause)
+            raise ValueError("plain columns next to aggregations without GROUP BY: %r" % (plain_cols or "*",))
         return q
 
 

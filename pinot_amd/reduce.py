@@ -8,6 +8,9 @@
                          max(limit*5, minServerGroupTrimSize) groups (GroupByUtils.getTableCapacity); without
                          ORDER BY keep `limit` groups (GroupByCombineOperator.java:63-73)
   final_result_table   ~ broker: extractFinalResult (AVG sum/count, HLL cardinality), ORDER BY, LIMIT
+  merge_selection      ~ broker: SelectionOperatorService.reduceWithOrdering / SelectionDataTableReducer (the servers'
+                         sorted rows merged under the ORDER BY comparator, `offset` rows dropped, `limit` kept,
+                         projected to the select list)
 """
 import math
 from functools import cmp_to_key
@@ -178,3 +181,28 @@ def final_result_table(res: IntermediateResult, query: Q.Query):
     for k, vals in rows:
         out.append([k[query.group_by.index(c)] for c in sel] + vals[:nsel])
     return out
+
+
+def merge_selection(results, query: Q.Query):
+    """Broker reduce of a selection: `results` are the servers' SelectionResults (engine.SelectionExecutor) in server
+    order, each sorted by the ORDER BY comparator. Merges them under that comparator (ties: server order, then the
+    server's own row order — the sort is stable), drops `offset` rows, keeps `limit`, and projects the rows to the select
+    list's order (`*`: the result's columns by name). Returns (column names, rows). Without ORDER BY the rows of the
+    servers are concatenated in server order (SelectionOperatorService.reduceWithoutOrdering)."""
+    from . import selection as S
+    results = list(results)
+    if not results:
+        return [], []
+    cols, types = results[0].columns, results[0].column_types
+    for r in results[1:]:
+        if list(r.columns) != list(cols):
+            raise ValueError("servers disagree on the selection's columns")
+    rows = [row for r in results for row in r.rows]
+    # stable sorts from the least significant ORDER BY column up
+    for ob in reversed(query.order_by):
+        i = cols.index(ob.expr)
+        rows.sort(key=lambda row, i=i, dt=types[i]: S.row_sort_key(row[i], dt), reverse=not ob.asc)
+    rows = rows[query.offset: query.offset + query.limit]
+    names = S.select_list(query, cols)
+    idx = [cols.index(c) for c in names]
+    return names, [[row[i] for i in idx] for row in rows]

@@ -4,8 +4,11 @@
              (and over a 10 % filter); the key space does not fit LDS, so accumulators are global
   star     : configs[4] shape on one GPU — raw DOUBLE SUM + DISTINCTCOUNTHLLMV over a multi-value column, 4-dim
              GROUP BY
+  selection: configs[1]'s table — SELECT impressions, clicks ... WHERE (the 10 % filter of bench.py's secondary line)
+             ORDER BY clicks DESC LIMIT 10 (selection_topk: the fused filter + top-K scan), and beside it
+             SELECT MAX(clicks) with the same WHERE (max_same_where: the same bytes through the lane kernels)
 
-python tools/bench_configs.py [--workload highcard|star|all] [--segments S] [--docs D] [--reps R]
+python tools/bench_configs.py [--workload highcard|star|selection|all] [--segments S] [--docs D] [--reps R]
 Prints one JSON line per (workload, plan): scan-kernel ms per launch (HIP events around back-to-back launches on
 the launch stream), rows/s, forward-index bytes staged per launch and GB/s, fetch ms, groups.
 """
@@ -256,6 +259,113 @@ def _bench():
     return _BENCH[0]
 
 
+def selection_check(gsegs, host, q, ids, days):
+    """selection_topk over the sample of segments kept on the host against a numpy top-K of the same segments: rows in
+    (clicks DESC, segment, doc) order, compared as (segment, doc, impressions, clicks)."""
+    from pinot_amd.engine import SelectionExecutor
+    from pinot_amd.segment import unpack_bits as unpack_all
+
+    def unpack_bits(buf, n, nb, chunk=1 << 20):  # (chunks of whole bytes: the decode's temporaries stay small)
+        return np.concatenate([unpack_all(buf[s * nb // 8:], min(chunk, n - s), nb) for s in range(0, n, chunk)])
+    ex = SelectionExecutor(q, gsegs[:len(host)])
+    got = ex.run()
+    ex.close()
+    seg_i, doc_i, clicks, imps = [], [], [], []
+    for si, sg in enumerate(host):
+        val = {n: np.asarray(sg.column(n).dictionary)[unpack_bits(sg.column(n).fwd_bytes, sg.num_docs, sg.column(n).num_bits)]
+               for n in ("daysSinceEpoch", "accountId", "clicks", "impressions")}
+        m = np.flatnonzero((val["daysSinceEpoch"] >= days[0]) & (val["daysSinceEpoch"] <= days[1]) &
+                           np.isin(val["accountId"], ids))
+        seg_i.append(np.full(len(m), si))
+        doc_i.append(m)
+        clicks.append(val["clicks"][m])
+        imps.append(val["impressions"][m])
+    seg_i, doc_i, clicks, imps = map(np.concatenate, (seg_i, doc_i, clicks, imps))
+    top = np.lexsort((doc_i, seg_i, -clicks))[:q.offset + q.limit]
+    want = [[int(clicks[i]), int(imps[i])] for i in top]
+    ok = (got.segments.tolist() == seg_i[top].tolist() and got.docs.tolist() == doc_i[top].tolist() and
+          [[int(r[0]), int(r[1])] for r in got.rows] == want)
+    return {"checked": bool(ok), "segments": len(host), "matched": int(len(doc_i))}
+
+
+def run_selection(nseg, docs, reps, warm=0, check=False, tuning=None, cpu_sample=0):
+    """The selection workload: selection_topk and max_same_where, scan ms per launch by HIP events around back-to-back
+    launches after `warm` untimed ones. Byte model of selection_topk: bench.algorithmic_bytes of its filter (staged
+    columns whole) + the ORDER BY column read per matching doc, sector-wise, + one 64-byte sector per output cell."""
+    import torch
+    from pinot_amd import parse_sql
+    from pinot_amd import _lib as L
+    from pinot_amd.engine import GpuQueryExecutor, GpuSegment, SelectionExecutor
+    B = _bench()
+    keep = max(cpu_sample, 2) if check else 0
+    gsegs, cids, host = [], None, []
+    for i in range(nseg):
+        seg = B.make_segment(100 + i, docs)
+        cids = cids or {n: j for j, n in enumerate(sorted(seg.columns))}
+        gsegs.append(GpuSegment(seg, column_ids=cids, device=0))
+        if len(host) < keep:
+            host.append(seg)
+            continue
+        for c in seg.columns.values():
+            c.fwd_bytes = None
+    ids = np.sort(np.random.default_rng(4242).choice(B.COLUMNS["accountId"][2](), size=B.SECONDARY[0][1], replace=False))
+    sec = B.secondary_query(B.SECONDARY[0][1])
+    where = sec[sec.index(" WHERE "):sec.index(" GROUP BY")]
+    stream = torch.cuda.current_stream()
+    sp = stream.cuda_stream
+    lines = (("selection_topk", "SELECT impressions, clicks FROM AdAnalyticsTable%s ORDER BY clicks DESC LIMIT 10" % where),
+             ("max_same_where", "SELECT MAX(clicks) FROM AdAnalyticsTable%s" % where))
+    for name, sql in lines:
+        q = parse_sql(sql)
+        ex = (SelectionExecutor if q.is_selection else GpuQueryExecutor)(q, gsegs, tuning=tuning)
+        ex.execute(sp)
+        for _ in range(warm):
+            ex.scan(sp)
+        torch.cuda.synchronize()
+        ex.reset(sp)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        for _ in range(reps):
+            ex.scan(sp)
+        b.record(stream)
+        torch.cuda.synchronize()
+        ms = a.elapsed_time(b) / reps
+        # reset + scan per launch: a selection's scans above start from the bound the earlier scans published (tighter
+        # than a fresh query's all-ones bound), so the figure of a fresh query is this one
+        a.record(stream)
+        for _ in range(reps):
+            ex.execute(sp)
+        b.record(stream)
+        torch.cuda.synchronize()
+        execute_ms = a.elapsed_time(b) / reps
+        ex.execute(sp)
+        t1 = time.perf_counter()
+        res = ex.fetch(sp, execution_stats=False)
+        fetch_ms = (time.perf_counter() - t1) * 1e3
+        matched = int(L.lib().pa_query_matched_docs(ex.handle))
+        algo = B.algorithmic_bytes(ex, matched)
+        out = {"workload": "selection", "plan_name": name, "kernel_ms": round(ms, 4),
+               "execute_ms": round(execute_ms, 4), "fetch_ms": round(fetch_ms, 2),
+               "matched_docs": matched, "plan": ex.stats()["plan"], "segments": nseg, "docs_per_segment": docs,
+               "warm": warm, "reps": reps}
+        if q.is_selection:
+            p = matched / max(1, nseg * docs)
+            nb = gsegs[0].segment.column("clicks").num_bits
+            algo += int(nseg * docs * nb / 8 * B._touched(p, 512 / nb)) + 64 * len(res.rows) * len(res.columns)
+            out.update(rows=len(res.rows), first_row=[int(v) for v in res.rows[0]] if res.rows else None,
+                       counters=ex.counters())
+            if check:
+                out["check"] = selection_check(gsegs, host, q, ids, B.DAY_RANGE)
+        else:
+            out["max"] = res.row[0]
+        out["roofline"] = {"bound": "hbm", "achieved": algo / (ms * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                           "frac": algo / (ms * 1e-3) / 1e9 / 8000.0, "algorithmic_bytes_per_launch": algo}
+        print(json.dumps(out), flush=True)
+        ex.close()
+    for g in gsegs:
+        g.close()
+
+
 def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None, cpu_sample=0, exec_stats=False,
         warm=0, check=False, tuning=None):
     import torch
@@ -413,6 +523,9 @@ def main():
                     for ps in (1, 2, 3) for wg in (0, 1, 2)]
     import torch
     torch.cuda.set_device(0)
+    if args.workload == "selection":
+        run_selection(args.segments, args.docs, args.reps, args.warm, args.check, tuning, args.cpu_sample)
+        return
     for w in (WORKLOADS if args.workload == "all" else [args.workload]):
         run(w, args.segments, args.docs, args.reps, args.plan, args.no_stepmajor, variants, args.cpu_sample,
             args.exec_stats, args.warm, args.check, tuning)
