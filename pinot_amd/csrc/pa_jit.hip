@@ -457,6 +457,9 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
     int rr = tn.gdl_rr >= 0 ? tn.gdl_rr : 64;
     while (rr > 1 && al16(rows + (size_t)(w / cd.rs) * lmax * rr * 8) + ring_img > kLdsBudget) rr >>= 1;
     while (rr > 1 && (rr & (rr - 1))) rr &= rr - 1;
+    // a row replica has to hold one tile of each wave that shares it (the drain period below, at least one tile): a
+    // c = 11 field holds 2047 docs, two waves' 1024-doc tiles on one replica are 2048
+    if (((uint64_t(1) << cbits) - 1) / (uint64_t)((64 / rr) * nd) / (uint64_t)cd.rs == 0) continue;
     const size_t ring = al16(rows + (size_t)(w / cd.rs) * lmax * rr * 8);
     const size_t total = ring + ring_img;
     if (total > kLdsBudget) continue;

@@ -1,6 +1,7 @@
 // HIP kernels of the segment query hot path other than the scan kernel (gfx950 / CDNA4 only): numGroupsLimit trimming,
 // segment-load and query-prep kernels, fetch compaction, partitioned pass C, and the launchers. The scan kernel's device
 // code is pa_scan.h; its variants are instantiated in pa_scan_std.hip / pa_scan_part_a.hip / pa_scan_part_b.hip.
+#include "pa_round.h"
 #include "pa_scan.h"
 
 namespace pa {
@@ -1189,40 +1190,6 @@ __global__ void __launch_bounds__(256) compact_gather_kernel(const unsigned long
   }
 }
 
-// Correctly rounded (nearest, ties to even) double of the signed 128-bit integer hi:lo — the host's (double)__int128 of
-// an exact 96-bit SUM (PA_ACC_SUM_I64X2), an int64 SUM or an integer MIN / MAX, computed with integer operations only.
-__device__ double i128_to_double(int64_t hi, uint64_t lo) {
-  const bool neg = hi < 0;
-  uint64_t mh = (uint64_t)hi, ml = lo;
-  if (neg) {
-    ml = ~ml + 1ull;
-    mh = ~mh + (ml == 0 ? 1ull : 0ull);
-  }
-  if (mh == 0 && ml < (1ull << 53)) return neg ? -(double)ml : (double)ml;  // (exact)
-  const int msb = mh ? 127 - __builtin_clzll(mh) : 63 - __builtin_clzll(ml);
-  const int s = msb - 52;  // bits below the 53-bit significand (>= 1 here)
-  auto bit = [&](int i) -> uint64_t { return i >= 64 ? (mh >> (i - 64)) & 1ull : (ml >> i) & 1ull; };
-  uint64_t sig = s >= 64 ? mh >> (s - 64) : ((ml >> s) | (mh << (64 - s)));
-  sig &= (1ull << 53) - 1ull;
-  sig |= 1ull << 52;  // (the leading bit; the masks above keep exactly 53 bits)
-  const uint64_t half = bit(s - 1);
-  bool sticky;
-  const int t = s - 1;  // bits [0, t) below the half bit
-  if (t <= 0) sticky = false;
-  else if (t >= 64) sticky = ml != 0 || (t > 64 && (mh & ((1ull << (t - 64)) - 1ull)) != 0);
-  else sticky = (ml & ((1ull << t) - 1ull)) != 0;
-  int e = s;
-  if (half && (sticky || (sig & 1ull))) {
-    ++sig;
-    if (sig == (1ull << 53)) {
-      sig >>= 1;
-      ++e;
-    }
-  }
-  const double d = ldexp((double)sig, e);
-  return neg ? -d : d;
-}
-
 // Block b covers keys [2048b, 2048b + 2048) as in compact_gather_kernel; positions first (thread t counts keys 8t..8t+7,
 // scans, and records each key's position in LDS), then thread t writes the rows of keys t + 256 j: consecutive threads,
 // consecutive rows, 8-byte columns stored as 512-byte wave bursts.
@@ -1270,9 +1237,10 @@ __global__ void __launch_bounds__(256) compact_final_kernel(const unsigned long 
         if (d.src[a] == SRC_LONG) {  // exact 96-bit total hi * 2^32 + lo, rounded once
           const int64_t hs = sv[2 * k + 1];
           const uint64_t ls = (uint64_t)sv[2 * k];
-          const uint64_t l0 = (uint64_t)hs << 32;
-          const uint64_t lo = l0 + ls;
-          v = i128_to_double((hs >> 32) + (lo < l0 ? 1 : 0), lo);
+          int64_t hi;
+          uint64_t lo;
+          sum_pair_to_i128(hs, ls, hi, lo);
+          v = i128_to_double(hi, lo);
         } else if (d.src[a] == SRC_INT || t == PA_AGG_COUNT_MV) {
           v = i128_to_double(sv[k] >> 63, (uint64_t)sv[k]);
         } else {
