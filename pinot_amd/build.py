@@ -6,14 +6,18 @@ import os
 import re
 import subprocess
 import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libpinot_amd.so")
-SOURCES = ["pa_scan_part_a.hip", "pa_scan_part_b.hip", "pa_scan_part_mv.hip", "pa_scan_std.hip", "pa_scan_lane.hip",
-           "pa_scan_gdense.hip", "pa_scan_select.hip", "pa_select.hip", "pa_kernels.hip", "pa_merge.hip", "pa_stats.hip", "pa_pve.hip", "pa_segment.hip",
-           "pa_plan.hip", "pa_plan_kernels.hip", "pa_jit.hip", "pa_capi.hip", "pa_fetch.hip", "pa_hist.hip",
-           "pa_stats_host.hip"]
+# slowest first: with fewer cores than units, the long compiles start at once and the short ones fill in behind them
+SOURCES = ["pa_scan_lane_lm.hip", "pa_scan_std.hip", "pa_scan_part_mv.hip", "pa_scan_part_b.hip", "pa_scan_lane_raw.hip",
+           "pa_scan_gdense.hip", "pa_scan_global.hip", "pa_scan_lane_dict.hip", "pa_kernels.hip", "pa_scan_part_a.hip",
+           "pa_stats.hip", "pa_stats_host.hip", "pa_scan_lane_sm.hip", "pa_scan_select.hip", "pa_plan.hip", "pa_jit.hip",
+           "pa_plan_kernels.hip", "pa_select.hip", "pa_fetch.hip", "pa_capi.hip", "pa_segment.hip", "pa_hist.hip",
+           "pa_merge.hip", "pa_pve.hip"]
 # every header under csrc/ (globbed, so a new one is covered without an edit here) and the public C-ABI header
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "pinot_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics", "-std=c++17",
@@ -93,16 +97,24 @@ def build(force=False, verbose=False):
         return LIB
     _jit_source()
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    # one object per stale source, compiled in parallel (each translation unit holds its own kernels), then one link
+    # one object per stale source (each translation unit holds its own kernels), at most MAX_JOBS compiles at a time,
+    # then one link
     todo = SOURCES if force else _stale_objs()
-    procs = []
-    for src in todo:
+    jobs = max(1, int(os.environ.get("MAX_JOBS", "16")))
+
+    def compile_one(src):
         cmd = [hipcc] + [f for f in FLAGS if f != "-shared"] + ["-c", os.path.join(CSRC, src), "-o", _obj(src) + ".tmp"]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
-        procs.append((src, subprocess.Popen(cmd)))
-    failed = [src for src, p in procs if p.wait() != 0]
-    for src, _ in procs:
+        t0 = time.time()
+        rc = subprocess.call(cmd)
+        if verbose:
+            print("%s: %.0f s" % (src, time.time() - t0), file=sys.stderr)
+        return rc
+
+    with ThreadPoolExecutor(max_workers=jobs) as pool:
+        failed = [src for src, rc in zip(todo, pool.map(compile_one, todo)) if rc != 0]
+    for src in todo:
         if src not in failed:
             os.replace(_obj(src) + ".tmp", _obj(src))
     if failed:

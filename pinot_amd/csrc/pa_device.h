@@ -1,4 +1,4 @@
-// Device-side descriptors shared by the scan kernels (pa_kernels.hip) and the host layer (pa_capi.hip).
+// Device-side descriptors shared by the device code (pa_scan.h, pa_kernels.hip) and the host layer (pa_capi.hip).
 //
 // Data layout in HBM (see DESIGN.md "Data layout"):
 //  * SV dictionary-encoded forward index: the reference's FixedBitSVForwardIndexWriter bitstream

@@ -1,6 +1,7 @@
 // HIP kernels of the segment query hot path other than the scan kernel (gfx950 / CDNA4 only): numGroupsLimit trimming,
 // segment-load and query-prep kernels, fetch compaction, partitioned pass C, and the launchers. The scan kernel's device
-// code is pa_scan.h; its variants are instantiated in pa_scan_std.hip / pa_scan_part_a.hip / pa_scan_part_b.hip.
+// code is pa_scan.h; its variants are instantiated in the pa_scan_*.hip units.
+#include <initializer_list>
 #include "pa_round.h"
 #include "pa_scan.h"
 
@@ -1962,7 +1963,8 @@ hipError_t launch_leap_search(const DevQuery* q, const DevSeg* segs, int64_t sli
 }
 
 static const void* scan_fn(int strategy, int steps, int lm) {
-  if (const void* f = scan_fn_std(strategy, steps, lm)) return f;
+  for (auto get : {scan_fn_std, scan_fn_global, scan_fn_lane_lm, scan_fn_lane_raw, scan_fn_lane_dict, scan_fn_lane_sm})
+    if (const void* f = get(strategy, steps, lm)) return f;
   if (const void* f = scan_fn_gdense(strategy, lm)) return f;
   if (const void* f = scan_fn_select(strategy, steps)) return f;
   if (const void* f = scan_fn_part_a(strategy)) return f;

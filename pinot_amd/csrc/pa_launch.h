@@ -1,4 +1,5 @@
-// Host-callable launchers of the kernels in pa_kernels.hip.
+// Host-callable launchers of the kernel units (pa_kernels.hip, pa_merge.hip, pa_stats.hip, pa_pve.hip) with their
+// descriptors.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pa_device.h"

@@ -1,5 +1,6 @@
 // Device code of the fused scan kernel (gfx950 / CDNA4 only): included by the translation units that instantiate its
-// variants (pa_scan_std.hip, pa_scan_part_a.hip, pa_scan_part_b.hip) and by pa_kernels.hip (the other kernels).
+// variants (pa_scan_std.hip, pa_scan_global.hip, pa_scan_lane_*.hip, pa_scan_part_*.hip, pa_scan_select.hip), by
+// pa_gdense.h and pa_select.hip for the helpers they share with it, and by pa_kernels.hip (the other kernels).
 //
 // HIP kernels of the segment query hot path.
 //
@@ -14,7 +15,7 @@
 // Work decomposition: a wave owns a contiguous range of 2048-doc "wave tiles" (all segments of the
 // query are concatenated); for each wave tile the forward-index words of every staged column are
 // copied HBM -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave instruction, fully coalesced)
-// into a wave-private double buffer, so tile t+1 streams in while tile t is decoded. Lane l decodes
+// into a wave-private ring of tile images, so tiles t+1 .. t+R-1 stream in while tile t is decoded. Lane l decodes
 // doc 64*i + l of the tile (i = 0..31): every column of a doc lands in the same lane, and a 64-doc
 // step of an nb-bit column is 2*nb consecutive LDS words (conflict-free ds_read2_b32).
 #pragma once
@@ -186,6 +187,40 @@ __device__ __forceinline__ int64_t wave_max_i64(int64_t v) {
   for (int o = 32; o > 0; o >>= 1) { const int64_t w = __shfl_xor(v, o); v = w > v ? w : v; }
   return v;
 }
+
+// Workgroups are dispatched to the 8 XCDs round-robin (block b runs on XCD b % 8). For queries that gather per matching
+// doc (dense), the scan gives block b the logical index of its place in XCD-major order, so the workgroups of one XCD
+// walk one contiguous eighth of the tiles: the segments (dictionaries, remaps) an XCD touches at a time are few, and
+// their lines stay in that XCD's L2 (configs[2]: HBM fetch of the emit pass 8.8 GB -> 0.9 GB per launch).
+__device__ __forceinline__ int64_t xcd_major_block(int64_t b, int64_t G) {
+  constexpr int kXcds = 8;
+  const int64_t x = b % kXcds, j = b / kXcds, per = G / kXcds, extra = G % kXcds;
+  return x * per + (x < extra ? x : extra) + j;
+}
+
+// What one wave of scan_kernel carries across its tiles, whatever the strategy. Which fields a strategy uses:
+//   pair, id, astr, idm            the aggregation-only strategies (is_lane), set by lane_acc_init
+//   leap_slice                     every strategy: the wave's index in logical (XCD-major) block order
+//   leap_n, leap_lds               every strategy with DevQuery::leap_mode (leap_tile)
+//   sel_*                          STRAT_SELECT, set by sel_state_init
+struct WaveState {
+  // Per-thread slots in LDS (the workgroup's lane-accumulator area at the front of the dynamic LDS: kLaneAccBytes per
+  // thread and aggregation), so no accumulator occupies a VGPR across the tile loop: aggregation a of thread t keeps
+  // (r0, r1) at pair + 16 * (a * WGS + t) and its dictId at id + 4 * (a * WGS + t) (consecutive threads 16 / 4 bytes
+  // apart: conflict-free ds_read_b128 / ds_read_b32).
+  uint32_t pair;   // LDS byte address of aggregation 0's (r0, r1) slot of this thread
+  uint32_t id;     // LDS byte address of aggregation 0's dictId slot of this thread
+  uint32_t astr;   // bytes between aggregations' pair slots (16 * WGS); dictId slots: astr / 4
+  uint32_t idm;    // bit a: aggregation a's dictId was updated in the current segment run
+  // fused execution statistics: this wave's slice of the E-doc list, the entries listed so far, and the LDS byte
+  // address of the wave's first leap_lds_cap entries (a global store in the tile loop would make the next tile's
+  // counted DMA wait longer: vmcnt counts stores too)
+  uint32_t leap_slice, leap_n, leap_lds;
+  // STRAT_SELECT (wave-uniform): candidates in the wave's segment of the scratch block, the wave's private bound
+  // (an entry is a candidate only while it is below it), counters, the LDS byte address of the wave's select state
+  uint32_t sel_n, sel_app, sel_cmp, sel_lds;
+  uint64_t sel_bk, sel_br;
+};
 
 // Value an aggregation reads for one doc. For HLL returns (register << 8) | rank.
 struct AggValue {
@@ -703,6 +738,98 @@ __device__ void accumulate_doc_mv(const DevQuery* __restrict__ q, const DevSeg* 
     // numGroupsLimit, walk form (direct key space): only the keys the segment admitted
     if (seg->admit != nullptr && !((gp(seg->admit)[key >> 5] >> (key & 31)) & 1u)) continue;
     update_doc_key<STRAT>(q, seg, img, doc_local, doc, key, acc);
+  }
+}
+
+// scan_kernel's prologue and epilogue of each strategy are functions next to that strategy's code (here: STRAT_LDS).
+// Their pointer parameters carry no __restrict__: the qualifier on an inlined helper gives its body alias scopes of
+// its own, and the kernels then compile differently.
+// STRAT_LDS, start of the kernel: the workgroup's LDS accumulators to their identities.
+template <int WGS>
+__device__ __forceinline__ void lds_acc_zero(const DevQuery* q, unsigned char* lds_acc) {
+  const int64_t K = q->num_keys;
+  uint32_t* cnt = (uint32_t*)(lds_acc + q->lds_count_off);
+  for (int64_t k = threadIdx.x; k < K; k += WGS) cnt[k] = 0;
+  for (int a = 0; a < q->num_aggs; ++a) {
+    const DevAgg& A = q->aggs[a];
+    if (A.type == PA_AGG_COUNT) continue;
+    if (A.type == PA_AGG_DISTINCTCOUNTHLL) {
+      uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
+      for (int64_t k = threadIdx.x; k < (K << A.log2m); k += WGS) r[k] = 0;
+    } else if (A.type == PA_AGG_DISTINCTCOUNT) {
+      uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
+      for (int64_t k = threadIdx.x; k < K * A.nvals / 4; k += WGS) r[k] = 0;
+    } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
+      uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
+      for (int64_t k = threadIdx.x; k < K * A.nvals; k += WGS) r[k] = 0;
+    } else {
+      int64_t* r = (int64_t*)(lds_acc + A.lds_off);
+      const int64_t init = A.type == PA_AGG_MIN ? INT64_MAX : (A.type == PA_AGG_MAX ? INT64_MIN : 0);  // SUM, COUNT_MV: 0
+      const int64_t n = (A.type == PA_AGG_SUM && A.src == SRC_LONG) ? 2 * K : K;
+      for (int64_t k = threadIdx.x; k < n; k += WGS) r[k] = init;  // SUM(double) 0.0 == all-zero bits
+    }
+  }
+  __syncthreads();
+}
+
+// STRAT_LDS, end of the kernel: every key the workgroup saw into the global accumulators.
+template <int WGS>
+__device__ __forceinline__ void lds_acc_flush(const DevQuery* q, unsigned char* lds_acc) {
+  __syncthreads();
+  const int64_t K = q->num_keys;
+  const uint32_t* cnt = (const uint32_t*)(lds_acc + q->lds_count_off);
+  for (int64_t k = threadIdx.x; k < K; k += WGS) {
+    const uint32_t c = cnt[k];
+    if (c == 0) continue;
+    __hip_atomic_fetch_add(gp(q->count) + k, (unsigned long long)c, RLX);
+    for (int a = 0; a < q->num_aggs; ++a) {
+      const DevAgg& A = q->aggs[a];
+      switch (A.type) {
+        case PA_AGG_SUM:
+          if (A.src == SRC_INT) {
+            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
+          } else if (A.src == SRC_LONG) {
+            const unsigned long long* r = (const unsigned long long*)(lds_acc + A.lds_off);
+            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k, r[2 * k], RLX);
+            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k + 1, r[2 * k + 1], RLX);
+          } else {
+            __hip_atomic_fetch_add(gp(A.acc_f64) + k, ((const double*)(lds_acc + A.lds_off))[k], RLX);
+          }
+          break;
+        case PA_AGG_COUNT_MV:
+          __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
+          break;
+        case PA_AGG_MIN: __hip_atomic_fetch_min(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
+        case PA_AGG_MAX: __hip_atomic_fetch_max(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
+        case PA_AGG_DISTINCTCOUNT: {  // presence words with a value seen here -> bytes of the global block
+          const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off + k * A.nvals);
+          AS1 uint8_t* g = gp(A.acc_hll) + k * A.nvals;
+          for (int64_t j = 0; j < A.nvals / 4; ++j) {
+            const uint32_t w = r[j];
+            if (w == 0) continue;
+            for (int b = 0; b < 4; ++b)
+              if ((w >> (8 * b)) & 0xffu) g[4 * j + b] = 1;
+          }
+        } break;
+        case PA_AGG_DISTINCTCOUNTHLL: {
+          const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off) + (k << A.log2m);
+          uint8_t* g = A.acc_hll + (k << A.log2m);
+          for (int j = 0; j < (1 << A.log2m); ++j)
+            if (r[j] != 0) atomic_max_u8(g + j, r[j]);
+        } break;
+        default: break;
+      }
+    }
+  }
+  // VALUE_HISTOGRAM: a row can hold tens of thousands of bins, so the workgroup's threads walk the bins of all keys
+  // (not one thread per key): every non-zero u32 bin becomes one u64 add into the global block
+  for (int a = 0; a < q->num_aggs; ++a) {
+    const DevAgg& A = q->aggs[a];
+    if (A.type != PA_AGG_VALUE_HISTOGRAM) continue;
+    const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off);
+    AS1 unsigned long long* g = gp((unsigned long long*)A.acc_i64);
+    for (int64_t i = threadIdx.x; i < K * A.nvals; i += WGS)
+      if (r[i] != 0) __hip_atomic_fetch_add(g + i, (unsigned long long)r[i], RLX);
   }
 }
 
@@ -2014,6 +2141,70 @@ __device__ __forceinline__ void part_tile(const DevQuery* __restrict__ q, const 
   }
 }
 
+// Count pass, start of the kernel: the workgroup's partition histogram to zero.
+template <int WGS>
+__device__ __forceinline__ void pcount_zero(const DevQuery* q, unsigned char* lds_acc) {
+  uint32_t* hist = (uint32_t*)lds_acc;
+  for (int p = threadIdx.x; p < q->num_parts; p += WGS) hist[p] = 0u;
+  __syncthreads();
+}
+
+// Count pass, end of the kernel: the histogram to the logical block's row.
+template <int WGS>
+__device__ __forceinline__ void pcount_store(const DevQuery* q, unsigned char* lds_acc, const PartScratch& ps,
+                                             int64_t lb) {
+  __syncthreads();
+  const uint32_t* hist = (const uint32_t*)lds_acc;
+  for (int p = threadIdx.x; p < q->num_parts; p += WGS) gp(ps.hist)[lb * q->num_parts + p] = hist[p];
+}
+
+// Emit pass, start of the kernel.
+template <int WGS>
+__device__ __forceinline__ void pemit_begin(const DevQuery* q, unsigned char* lds_acc, const PartScratch& ps) {
+  // every partition's bin empty; its range in the stream: the partition base + this workgroup's offset (part_scan),
+  // holding exactly the records the count pass counted here
+  const BinState B = bin_state(q, lds_acc);
+  const int64_t lbi = q->xcd_major ? xcd_major_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int P = q->num_parts, pv = q->pv;
+  for (int p = q->part_lo + threadIdx.x; p < q->part_hi; p += WGS) {
+    B.cnt[p] = 0u;
+    B.done[p] = 0u;
+    B.front[p] = 0u;
+    if (p >= pv) B.slk[p] = 0u;
+    B.back[p] = gp(ps.hist)[lbi * P + p];
+    B.start[p] = gp(ps.base)[p < pv ? p : p + 1] + gp(ps.off)[lbi * P + p];
+  }
+  __syncthreads();
+}
+
+// Emit pass, end of the kernel (lb: the logical block).
+template <int WGS>
+__device__ __forceinline__ void pemit_finish(const DevQuery* q, unsigned char* lds_acc, const PartScratch& ps,
+                                             int64_t lb) {
+  // every bin's rest (< one bin) between the range's front and back, then sentinel records up to the padded end
+  __syncthreads();
+  const BinState B = bin_state(q, lds_acc);
+  const int P = q->num_parts, pv = q->pv;
+  for (int p = q->part_lo + threadIdx.x; p < q->part_hi; p += WGS) {
+    const bool isv = p < pv;
+    const uint32_t nw = isv ? (uint32_t)q->rec_words_v : 1u;
+    const uint32_t BS = (uint32_t)(isv ? q->bs_v : q->bs_h);
+    const lds_u32_t* bin = isv ? lds_ptr(lds_acc + q->lds_bins_v) + (uint32_t)p * BS * nw
+                               : lds_ptr(lds_acc + q->lds_bins_h) + (uint32_t)(p - pv) * (BS + (uint32_t)kDocVals);
+    AS1 uint32_t* recs = gp(isv ? ps.recs_v : ps.recs_h);
+    const uint32_t n = B.cnt[p], o = B.front[p];
+    const uint32_t h = gp(ps.hist)[lb * P + p];
+    if ((n >= BS || o + n != B.back[p]) && !q->debug_emit)  // the emit pass must see exactly the count pass's records
+      __hip_atomic_fetch_add(gp(q->matched_docs) + 3, 1ull, RLX);
+    AS1 uint32_t* d = recs + (B.start[p] + o) * (uint64_t)nw;
+    const uint32_t nn = n < BS ? n : BS;
+    for (uint32_t e = 0; e < nn * nw; ++e) d[e] = bin[e];
+    const uint32_t padded = (h + BS - 1u) / BS * BS;
+    AS1 uint32_t* z = recs + (B.start[p] + h) * (uint64_t)nw;
+    for (uint32_t e = 0; e < (padded - h) * nw; ++e) z[e] = (e % nw) == 0 ? kSentinel : 0u;
+  }
+}
+
 // numGroupsLimit (walk form): the docs of match words m whose table-wide group key is admitted in this segment
 // (seg->admit, written by limit_walk_kernel). Eight steps per batch: every dictId decode, then every remap gather, then
 // every bitmap gather (their latencies overlap).
@@ -2067,45 +2258,27 @@ __device__ __forceinline__ uint32_t admitted_docs(const DevQuery* __restrict__ q
 // over the block's values), Min/MaxAggregationFunction.aggregate.
 // MIN / MAX over a sorted dictionary run on dictIds (rid[a]: the lane's min / max dictId within the current segment),
 // folded into r0 as a value at the end of every segment run (lane_acc_segment_end).
-struct LaneAcc {
-  // Per-thread slots in LDS (the workgroup's lane-accumulator area at the front of the dynamic LDS: kLaneAccBytes per
-  // thread and aggregation), so no accumulator occupies a VGPR across the tile loop: aggregation a of thread t keeps
-  // (r0, r1) at pair + 16 * (a * WGS + t) and its dictId at id + 4 * (a * WGS + t) (consecutive threads 16 / 4 bytes
-  // apart: conflict-free ds_read_b128 / ds_read_b32).
-  uint32_t pair;   // LDS byte address of aggregation 0's (r0, r1) slot of this thread
-  uint32_t id;     // LDS byte address of aggregation 0's dictId slot of this thread
-  uint32_t astr;   // bytes between aggregations' pair slots (16 * WGS); dictId slots: astr / 4
-  uint32_t idm;    // bit a: aggregation a's dictId was updated in the current segment run
-  // fused execution statistics: this wave's slice of the E-doc list, the entries listed so far, and the LDS byte
-  // address of the wave's first leap_lds_cap entries (a global store in the tile loop would make the next tile's
-  // counted DMA wait longer: vmcnt counts stores too)
-  uint32_t leap_slice, leap_n, leap_lds;
-  // STRAT_SELECT (wave-uniform): candidates in the wave's segment of the scratch block, the wave's private bound
-  // (an entry is a candidate only while it is below it), counters, the LDS byte address of the wave's select state
-  uint32_t sel_n, sel_app, sel_cmp, sel_lds;
-  uint64_t sel_bk, sel_br;
-};
 typedef __attribute__((address_space(3))) int64_t lds_i64_t;
-__device__ __forceinline__ void la_get(const LaneAcc& la, int a, int64_t& r0, int64_t& r1) {
+__device__ __forceinline__ void la_get(const WaveState& la, int a, int64_t& r0, int64_t& r1) {
   const lds_i64_t* p = (const lds_i64_t*)(uintptr_t)(la.pair + (uint32_t)a * la.astr);
   r0 = p[0];
   r1 = p[1];
 }
-__device__ __forceinline__ void la_set(const LaneAcc& la, int a, int64_t r0, int64_t r1) {
+__device__ __forceinline__ void la_set(const WaveState& la, int a, int64_t r0, int64_t r1) {
   lds_i64_t* p = (lds_i64_t*)(uintptr_t)(la.pair + (uint32_t)a * la.astr);
   p[0] = r0;
   p[1] = r1;
 }
-__device__ __forceinline__ uint32_t la_rid(const LaneAcc& la, int a) {
+__device__ __forceinline__ uint32_t la_rid(const WaveState& la, int a) {
   return *(const lds_u32_t*)(uintptr_t)(la.id + (uint32_t)a * (la.astr >> 2));
 }
-__device__ __forceinline__ void la_set_rid(const LaneAcc& la, int a, uint32_t v) {
+__device__ __forceinline__ void la_set_rid(const WaveState& la, int a, uint32_t v) {
   *(lds_u32_t*)(uintptr_t)(la.id + (uint32_t)a * (la.astr >> 2)) = v;
 }
 
 __device__ __forceinline__ uint32_t rid_init(int t) { return t == PA_AGG_MIN ? 0xffffffffu : 0u; }
 
-__device__ __forceinline__ void lane_acc_init(const DevQuery* __restrict__ q, LaneAcc& la, const void* lds_area,
+__device__ __forceinline__ void lane_acc_init(const DevQuery* __restrict__ q, WaveState& la, const void* lds_area,
                                               int wgs) {
   la.astr = 16u * (uint32_t)wgs;
   la.pair = lds_addr(lds_area) + 16u * threadIdx.x;
@@ -2203,7 +2376,7 @@ __device__ __noinline__ void lane_agg_lm_any(int nb, uint32_t region_lds, int la
 // End of a wave's run over one segment: MIN / MAX dictIds of the segment -> values, folded into r0 (only when the
 // lane kept some doc of the segment: a MAX dictId of 0 is otherwise meaningless).
 __device__ __forceinline__ void lane_acc_segment_end(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
-                                                     LaneAcc& la, bool any) {
+                                                     WaveState& la, bool any) {
 #pragma unroll
   for (int a = 0; a < kLaneAggs; ++a) {
     if (a >= q->num_aggs) break;
@@ -2354,7 +2527,7 @@ __device__ __forceinline__ void lane_raw_dense(const char* tile, uint32_t m, int
 template <int LM, int STEPS, int STRAT>
 __device__ __forceinline__ void lane_acc_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                               const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
-                                              LaneAcc& la, unsigned char* lds) {
+                                              WaveState& la, unsigned char* lds) {
   typedef const __attribute__((address_space(4))) DevSeg CSeg;
   CSeg* cs = (CSeg*)(uintptr_t)seg;
   auto local = [&](int i) { return LM ? 32 * lane + i : i * kWave + lane; };
@@ -2511,7 +2684,7 @@ __device__ __forceinline__ void lane_acc_tile(const DevQuery* __restrict__ q, co
 }
 
 // End of the kernel: one wave reduction per accumulator and one device-scope atomic per wave.
-__device__ __forceinline__ void lane_acc_flush(const DevQuery* __restrict__ q, const LaneAcc& la, int lane) {
+__device__ __forceinline__ void lane_acc_flush(const DevQuery* __restrict__ q, const WaveState& la, int lane) {
 #pragma unroll
   for (int a = 0; a < kLaneAggs; ++a) {
     if (a >= q->num_aggs) break;
@@ -2540,6 +2713,51 @@ __device__ __forceinline__ void lane_acc_flush(const DevQuery* __restrict__ q, c
       const int64_t r = wave_max_i64(r0);
       if (lane == 0 && r != INT64_MIN) __hip_atomic_fetch_max(gp((long long*)A.acc_i64), (long long)r, RLX);
     }
+  }
+}
+
+// STRAT_LANE_DICT, start of the kernel: the dictId histograms of SUMs over a shared dictionary to zero.
+template <int WGS>
+__device__ __forceinline__ void lane_hist_zero(const DevQuery* q, unsigned char* lds_acc) {
+  for (int a = 0; a < q->num_aggs; ++a) {
+    const int hc = q->aggs[a].hist_card;
+    if (hc <= 0) continue;
+    uint32_t* h = (uint32_t*)(lds_acc + q->aggs[a].hist_off);
+    for (int i = threadIdx.x; i < hc; i += WGS) h[i] = 0u;
+  }
+  __syncthreads();
+}
+
+// STRAT_LANE_DICT, end of the kernel, before lane_acc_flush.
+template <int WGS>
+__device__ __forceinline__ void lane_hist_fold(const DevQuery* q, const DevSeg* segs, unsigned char* lds_acc,
+                                               const WaveState& la) {
+  // each thread folds histogram entries t, t + WGS, ... : count * value into its lane accumulator (exact split
+  // pair for 64-bit values: count < 2^32, so count * low32 and count * high32 fit their int64 halves)
+  __syncthreads();
+  for (int a = 0; a < q->num_aggs; ++a) {
+    const DevAgg& A = q->aggs[a];
+    if (A.hist_card <= 0) continue;
+    const uint32_t* h = (const uint32_t*)(lds_acc + A.hist_off);
+    const DevCol& c = segs[0].cols[A.slot];
+    int64_t r0, r1;
+    la_get(la, a, r0, r1);
+    for (int i = threadIdx.x; i < A.hist_card; i += WGS) {
+      const uint32_t n = h[i];
+      if (n == 0) continue;
+      if (A.src == SRC_DOUBLE) {
+        r0 = __builtin_bit_cast(int64_t, __builtin_bit_cast(double, r0) + (double)n * gp(c.dict_f64)[i]);
+      } else {
+        const int64_t v = gp(c.dict_i64)[i];
+        if (A.src == SRC_INT) {
+          r0 += (int64_t)n * v;
+        } else {
+          r0 += (int64_t)n * (int64_t)(uint32_t)v;
+          r1 += (int64_t)n * (v >> 32);
+        }
+      }
+    }
+    la_set(la, a, r0, r1);
   }
 }
 
@@ -2715,7 +2933,7 @@ __device__ __forceinline__ uint64_t sel_component(CSelCol* cp, int width, int sh
 // The docs of one tile that passed the filter (bit i of m: the lane's doc of step i) offered to the wave's candidates.
 template <int STEPS, int LM>
 __device__ __forceinline__ void select_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
-                                            const uint32_t* img, int64_t doc_base, uint32_t m, int lane, LaneAcc& la) {
+                                            const uint32_t* img, int64_t doc_base, uint32_t m, int lane, WaveState& la) {
   CSel* S = (CSel*)(uintptr_t)q->sel;
   const int nob = S->nob;
   const uint32_t K = (uint32_t)S->K, CAP = (uint32_t)S->cap;
@@ -2760,13 +2978,36 @@ __device__ __forceinline__ void select_tile(const DevQuery* __restrict__ q, cons
   }
 }
 
+// Start of the kernel: no candidate yet, the bound all ones; the wave's select state in LDS.
+__device__ __forceinline__ void sel_state_init(WaveState& la, const uint32_t* smem, int wave) {
+  la.sel_n = la.sel_app = la.sel_cmp = 0u;
+  la.sel_bk = la.sel_br = ~0ull;
+  la.sel_lds = lds_addr(smem) + (uint32_t)wave * (uint32_t)(kSelLdsWords * 4);
+}
+
+// End of a segment run: the segment's matched docs (its share of numEntriesScannedPostFilter).
+__device__ __forceinline__ void sel_segment_docs(const DevQuery* q, const DevSeg* seg, uint32_t matched,
+                                                 uint32_t matched_seg0, int lane) {
+  const int64_t sm = wave_sum_i64((int64_t)(matched - matched_seg0));
+  if (lane == 0 && sm != 0) __hip_atomic_fetch_add(gp(q->sel->seg_docs) + seg->index, (unsigned long long)sm, RLX);
+}
+
+// End of the kernel, every wave: the finish kernels read every wave's count.
+__device__ __forceinline__ void sel_counters_flush(const DevQuery* q, const WaveState& la, int lane) {
+  if (lane == 0) {
+    gp(q->sel->wave_n)[la.leap_slice] = la.sel_n;
+    if (la.sel_app) __hip_atomic_fetch_add(gp(q->sel->counters), (unsigned long long)la.sel_app, RLX);
+    if (la.sel_cmp) __hip_atomic_fetch_add(gp(q->sel->counters) + 1, (unsigned long long)la.sel_cmp, RLX);
+  }
+}
+
 // The rare part of a tile (some doc survived the eager clauses): lazy clauses per surviving doc, then aggregation.
 // Returns the docs that matched.
 // LM: doc of bit i of lane l = 32l + i (lane-major tile), else 64i + l.
 template <int STRAT, int STEPS, int LM>
 __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg_in,
                                                 const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
-                                                unsigned char* lds, const PartScratch& ps, LaneAcc& la) {
+                                                unsigned char* lds, const PartScratch& ps, WaveState& la) {
   const DevSeg* __restrict__ seg = uniform_ptr(seg_in);
   doc_base = ((int64_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)doc_base >> 32)) << 32) |
              (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)doc_base);
@@ -2809,7 +3050,6 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
     if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_tile<LM, STEPS, STRAT>(q, seg, img, doc_base, m, lane, la, lds);
   } else if constexpr (is_pcount(STRAT) || is_pemit(STRAT)) {
     part_tile<STRAT, STEPS, LM>(q, seg, img, doc_base, m, lane, lds, ps);
-
   } else if (q->has_mv) {
     for (int i = 0; i < STEPS; ++i)
       if ((m >> i) & 1u) accumulate_doc_mv<STRAT>(q, seg, img, local(i), doc_base + local(i), acc);
@@ -2829,9 +3069,6 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
     } else {
       accumulate_lds_lm<4>(q, seg, img, doc_base, m, lane, lds);
     }
-  } else if (q->has_mv) {
-    for (int i = 0; i < STEPS; ++i)
-      if ((m >> i) & 1u) accumulate_doc_mv<STRAT>(q, seg, img, local(i), doc_base + local(i), acc);
   } else {
     for (int i = 0; i < STEPS; ++i) {
       const uint64_t sm = __ballot((m >> i) & 1u);
@@ -2846,7 +3083,7 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
 template <int STRAT, int STEPS>
 __device__ __forceinline__ void process_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                              int64_t wt, const uint32_t* img, int lane, const Acc<STRAT>& acc,
-                                             uint32_t& matched, LaneAcc& la) {
+                                             uint32_t& matched, WaveState& la) {
   const int64_t doc_base = wt * (STEPS * kWave);
   // docs of this tile owned by the lane: 64*i + lane < rem
   const int64_t rem = (int64_t)seg->num_docs - doc_base;
@@ -2997,7 +3234,7 @@ __device__ __forceinline__ void stage_tile_lm(uint32_t ip, int64_t wt, uint32_t 
 template <int STRAT>
 __device__ __forceinline__ void process_tile_lm(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                                 uint32_t pp, int64_t wt, const uint32_t* img, uint32_t img_lds,
-                                                int lane, const Acc<STRAT>& acc, uint32_t& matched, LaneAcc& la) {
+                                                int lane, const Acc<STRAT>& acc, uint32_t& matched, WaveState& la) {
   const int64_t doc_base = wt * kWTileDocs;
   const int64_t rem = (int64_t)(int32_t)rl(pp, 2) - doc_base;
   uint32_t valid = 0xffffffffu;
@@ -3103,16 +3340,6 @@ __device__ __forceinline__ void lm_wait_issue(const LmIssue& I, uint32_t& slot_o
   for (; issued < D; ++issued) dma16_masked(I.dummy, dst0, 1ull);
 }
 
-// Workgroups are dispatched to the 8 XCDs round-robin (block b runs on XCD b % 8). For queries that gather per matching
-// doc (dense), the scan gives block b the logical index of its place in XCD-major order, so the workgroups of one XCD
-// walk one contiguous eighth of the tiles: the segments (dictionaries, remaps) an XCD touches at a time are few, and
-// their lines stay in that XCD's L2 (configs[2]: HBM fetch of the emit pass 8.8 GB -> 0.9 GB per launch).
-__device__ __forceinline__ int64_t xcd_major_block(int64_t b, int64_t G) {
-  constexpr int kXcds = 8;
-  const int64_t x = b % kXcds, j = b / kXcds, per = G / kXcds, extra = G % kXcds;
-  return x * per + (x < extra ? x : extra) + j;
-}
-
 // The V-only emit of 4-wave workgroups (one whole tile per batch in part_tile): compiled for 2 workgroups per CU.
 __host__ __device__ constexpr bool emit_v_wide(int s) {
   return is_pemit(s) && !pemit_hh(s) && !pemit_big(s) && pemit_vf(s) != V_FMT_GEN;
@@ -3137,75 +3364,24 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   uint32_t* ring = smem + acc_dwords + wave * q->ring * img_dw;
   Acc<STRAT> acc{q, lds_acc, &ps};
 
-  if (STRAT == STRAT_LDS) {
-    const int64_t K = q->num_keys;
-    uint32_t* cnt = (uint32_t*)(lds_acc + q->lds_count_off);
-    for (int64_t k = threadIdx.x; k < K; k += WGS) cnt[k] = 0;
-    for (int a = 0; a < q->num_aggs; ++a) {
-      const DevAgg& A = q->aggs[a];
-      if (A.type == PA_AGG_COUNT) continue;
-      if (A.type == PA_AGG_DISTINCTCOUNTHLL) {
-        uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
-        for (int64_t k = threadIdx.x; k < (K << A.log2m); k += WGS) r[k] = 0;
-      } else if (A.type == PA_AGG_DISTINCTCOUNT) {
-        uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
-        for (int64_t k = threadIdx.x; k < K * A.nvals / 4; k += WGS) r[k] = 0;
-      } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
-        uint32_t* r = (uint32_t*)(lds_acc + A.lds_off);
-        for (int64_t k = threadIdx.x; k < K * A.nvals; k += WGS) r[k] = 0;
-      } else {
-        int64_t* r = (int64_t*)(lds_acc + A.lds_off);
-        const int64_t init = A.type == PA_AGG_MIN ? INT64_MAX : (A.type == PA_AGG_MAX ? INT64_MIN : 0);  // SUM, COUNT_MV: 0
-        const int64_t n = (A.type == PA_AGG_SUM && A.src == SRC_LONG) ? 2 * K : K;
-        for (int64_t k = threadIdx.x; k < n; k += WGS) r[k] = init;  // SUM(double) 0.0 == all-zero bits
-      }
-    }
-    __syncthreads();
-  } else if (is_pcount(STRAT)) {
-    uint32_t* hist = (uint32_t*)lds_acc;
-    for (int p = threadIdx.x; p < q->num_parts; p += WGS) hist[p] = 0u;
-    __syncthreads();
-  } else if (is_pemit(STRAT)) {
-    // every partition's bin empty; its range in the stream: the partition base + this workgroup's offset (part_scan),
-    // holding exactly the records the count pass counted here
-    const BinState B = bin_state(q, lds_acc);
-    const int64_t lbi = q->xcd_major ? xcd_major_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
-    const int P = q->num_parts, pv = q->pv;
-    for (int p = q->part_lo + threadIdx.x; p < q->part_hi; p += WGS) {
-      B.cnt[p] = 0u;
-      B.done[p] = 0u;
-      B.front[p] = 0u;
-      if (p >= pv) B.slk[p] = 0u;
-      B.back[p] = gp(ps.hist)[lbi * P + p];
-      B.start[p] = gp(ps.base)[p < pv ? p : p + 1] + gp(ps.off)[lbi * P + p];
-    }
-    __syncthreads();
-  }
+  if (STRAT == STRAT_LDS) lds_acc_zero<WGS>(q, lds_acc);
+  else if (is_pcount(STRAT)) pcount_zero<WGS>(q, lds_acc);
+  else if (is_pemit(STRAT)) pemit_begin<WGS>(q, lds_acc, ps);
 
   uint32_t matched = 0;  // docs of this lane that passed the filter (numDocsScanned)
-  LaneAcc la;
+  WaveState la;
   la.leap_slice = (uint32_t)((q->xcd_major ? xcd_major_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x) * WPW + wave);
   la.leap_n = 0u;
   la.leap_lds = lds_addr(smem + acc_dwords + (uint32_t)WPW * (uint32_t)q->ring * (uint32_t)img_dw) +
                 (uint32_t)wave * (uint32_t)q->leap_lds_cap * 8u;
   if constexpr (is_lane(STRAT) && STRAT != STRAT_LANE_CNT) lane_acc_init(q, la, smem, WGS);
-  if constexpr (STRAT == STRAT_SELECT) {  // no candidate yet, the bound all ones; the wave's select state in LDS
-    la.sel_n = la.sel_app = la.sel_cmp = 0u;
-    la.sel_bk = la.sel_br = ~0ull;
-    la.sel_lds = lds_addr(smem) + (uint32_t)wave * (uint32_t)(kSelLdsWords * 4);
-  }
-  if constexpr (STRAT == STRAT_LANE_DICT) {  // the dictId histograms of SUMs over a shared dictionary
-    for (int a = 0; a < q->num_aggs; ++a) {
-      const int hc = q->aggs[a].hist_card;
-      if (hc <= 0) continue;
-      uint32_t* h = (uint32_t*)(lds_acc + q->aggs[a].hist_off);
-      for (int i = threadIdx.x; i < hc; i += WGS) h[i] = 0u;
-    }
-    __syncthreads();
-  }
+  if constexpr (STRAT == STRAT_SELECT) sel_state_init(la, smem, wave);
+  if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_zero<WGS>(q, lds_acc);
   const int64_t T = q->total_wtiles;
   const int64_t W = (int64_t)gridDim.x * WPW;
-  const int64_t lb = q->xcd_major ? xcd_major_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;  // logical block
+  // logical block: also derived in pemit_begin and for la.leap_slice above; deriving it once changes every scan kernel's
+  // registers and code size (as does moving the leap-list write-out below into a function), so the copies stay
+  const int64_t lb = q->xcd_major ? xcd_major_block(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
   const int64_t gw = lb * WPW + wave;
   const int64_t t0 = gw * T / W;
   const int64_t t1 = (gw + 1) * T / W;
@@ -3334,10 +3510,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
         pslot = pslot + 1 == R ? 0 : pslot + 1;
       }
       if constexpr (is_lane(STRAT) && STRAT != STRAT_LANE_CNT) lane_acc_segment_end(q, seg, la, matched != matched_seg0);
-      if constexpr (STRAT == STRAT_SELECT) {  // the segment's matched docs (its share of numEntriesScannedPostFilter)
-        const int64_t sm = wave_sum_i64((int64_t)(matched - matched_seg0));
-        if (lane == 0 && sm != 0) __hip_atomic_fetch_add(gp(q->sel->seg_docs) + seg->index, (unsigned long long)sm, RLX);
-      }
+      if constexpr (STRAT == STRAT_SELECT) sel_segment_docs(q, seg, matched, matched_seg0, lane);
       if (t < t1) {
         ++si;
         while (t >= segs[si].first_wtile + segs[si].num_wtiles) ++si;
@@ -3355,143 +3528,29 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
       for (uint32_t k = (uint32_t)lane; k < nl; k += kWave) list[k] = ll[k];
       if (lane == 0) gp(q->leap_out)[3 * (int64_t)q->num_segments + 1 + la.leap_slice] = la.leap_n;
     }
-  if constexpr (STRAT == STRAT_SELECT) {  // every wave: the finish kernels read every wave's count
-    if (lane == 0) {
-      gp(q->sel->wave_n)[la.leap_slice] = la.sel_n;
-      if (la.sel_app) __hip_atomic_fetch_add(gp(q->sel->counters), (unsigned long long)la.sel_app, RLX);
-      if (la.sel_cmp) __hip_atomic_fetch_add(gp(q->sel->counters) + 1, (unsigned long long)la.sel_cmp, RLX);
-    }
-  }
+  if constexpr (STRAT == STRAT_SELECT) sel_counters_flush(q, la, lane);
   if (!is_pemit(STRAT)) {  // (the partitioned count pass counts numDocsScanned; its emit pass sees the same docs)
     const int64_t wm = wave_sum_i64((int64_t)matched);
     if (lane == 0 && wm != 0) __hip_atomic_fetch_add(gp(q->matched_docs), (unsigned long long)wm, RLX);
     if constexpr (is_lane(STRAT)) {  // COUNT(*) of an aggregation-only query = the docs the filter kept
       if (lane == 0 && wm != 0) __hip_atomic_fetch_add(gp(q->count), (unsigned long long)wm, RLX);
-      if constexpr (STRAT == STRAT_LANE_DICT) {
-        // each thread folds histogram entries t, t + WGS, ... : count * value into its lane accumulator (exact split
-        // pair for 64-bit values: count < 2^32, so count * low32 and count * high32 fit their int64 halves)
-        __syncthreads();
-        for (int a = 0; a < q->num_aggs; ++a) {
-          const DevAgg& A = q->aggs[a];
-          if (A.hist_card <= 0) continue;
-          const uint32_t* h = (const uint32_t*)(lds_acc + A.hist_off);
-          const DevCol& c = segs[0].cols[A.slot];
-          int64_t r0, r1;
-          la_get(la, a, r0, r1);
-          for (int i = threadIdx.x; i < A.hist_card; i += WGS) {
-            const uint32_t n = h[i];
-            if (n == 0) continue;
-            if (A.src == SRC_DOUBLE) {
-              r0 = __builtin_bit_cast(int64_t, __builtin_bit_cast(double, r0) + (double)n * gp(c.dict_f64)[i]);
-            } else {
-              const int64_t v = gp(c.dict_i64)[i];
-              if (A.src == SRC_INT) {
-                r0 += (int64_t)n * v;
-              } else {
-                r0 += (int64_t)n * (int64_t)(uint32_t)v;
-                r1 += (int64_t)n * (v >> 32);
-              }
-            }
-          }
-          la_set(la, a, r0, r1);
-        }
-      }
+      if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_fold<WGS>(q, segs, lds_acc, la);
       if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_flush(q, la, lane);
     }
   }
-  if (is_pcount(STRAT)) {
-    __syncthreads();
-    const uint32_t* hist = (const uint32_t*)lds_acc;
-    for (int p = threadIdx.x; p < q->num_parts; p += WGS) gp(ps.hist)[lb * q->num_parts + p] = hist[p];
-  }
-  if (is_pemit(STRAT)) {
-    // every bin's rest (< one bin) between the range's front and back, then sentinel records up to the padded end
-    __syncthreads();
-    const BinState B = bin_state(q, lds_acc);
-    const int P = q->num_parts, pv = q->pv;
-    for (int p = q->part_lo + threadIdx.x; p < q->part_hi; p += WGS) {
-      const bool isv = p < pv;
-      const uint32_t nw = isv ? (uint32_t)q->rec_words_v : 1u;
-      const uint32_t BS = (uint32_t)(isv ? q->bs_v : q->bs_h);
-      const lds_u32_t* bin = isv ? lds_ptr(lds_acc + q->lds_bins_v) + (uint32_t)p * BS * nw
-                                 : lds_ptr(lds_acc + q->lds_bins_h) + (uint32_t)(p - pv) * (BS + (uint32_t)kDocVals);
-      AS1 uint32_t* recs = gp(isv ? ps.recs_v : ps.recs_h);
-      const uint32_t n = B.cnt[p], o = B.front[p];
-      const uint32_t h = gp(ps.hist)[lb * P + p];
-      if ((n >= BS || o + n != B.back[p]) && !q->debug_emit)  // the emit pass must see exactly the count pass's records
-        __hip_atomic_fetch_add(gp(q->matched_docs) + 3, 1ull, RLX);
-      AS1 uint32_t* d = recs + (B.start[p] + o) * (uint64_t)nw;
-      const uint32_t nn = n < BS ? n : BS;
-      for (uint32_t e = 0; e < nn * nw; ++e) d[e] = bin[e];
-      const uint32_t padded = (h + BS - 1u) / BS * BS;
-      AS1 uint32_t* z = recs + (B.start[p] + h) * (uint64_t)nw;
-      for (uint32_t e = 0; e < (padded - h) * nw; ++e) z[e] = (e % nw) == 0 ? kSentinel : 0u;
-    }
-  }
-  if (STRAT == STRAT_LDS) {
-    __syncthreads();
-    const int64_t K = q->num_keys;
-    const uint32_t* cnt = (const uint32_t*)(lds_acc + q->lds_count_off);
-    for (int64_t k = threadIdx.x; k < K; k += WGS) {
-      const uint32_t c = cnt[k];
-      if (c == 0) continue;
-      __hip_atomic_fetch_add(gp(q->count) + k, (unsigned long long)c, RLX);
-      for (int a = 0; a < q->num_aggs; ++a) {
-        const DevAgg& A = q->aggs[a];
-        switch (A.type) {
-          case PA_AGG_SUM:
-            if (A.src == SRC_INT) {
-              __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
-            } else if (A.src == SRC_LONG) {
-              const unsigned long long* r = (const unsigned long long*)(lds_acc + A.lds_off);
-              __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k, r[2 * k], RLX);
-              __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k + 1, r[2 * k + 1], RLX);
-            } else {
-              __hip_atomic_fetch_add(gp(A.acc_f64) + k, ((const double*)(lds_acc + A.lds_off))[k], RLX);
-            }
-            break;
-          case PA_AGG_COUNT_MV:
-            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
-            break;
-          case PA_AGG_MIN: __hip_atomic_fetch_min(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
-          case PA_AGG_MAX: __hip_atomic_fetch_max(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
-          case PA_AGG_DISTINCTCOUNT: {  // presence words with a value seen here -> bytes of the global block
-            const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off + k * A.nvals);
-            AS1 uint8_t* g = gp(A.acc_hll) + k * A.nvals;
-            for (int64_t j = 0; j < A.nvals / 4; ++j) {
-              const uint32_t w = r[j];
-              if (w == 0) continue;
-              for (int b = 0; b < 4; ++b)
-                if ((w >> (8 * b)) & 0xffu) g[4 * j + b] = 1;
-            }
-          } break;
-          case PA_AGG_DISTINCTCOUNTHLL: {
-            const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off) + (k << A.log2m);
-            uint8_t* g = A.acc_hll + (k << A.log2m);
-            for (int j = 0; j < (1 << A.log2m); ++j)
-              if (r[j] != 0) atomic_max_u8(g + j, r[j]);
-          } break;
-          default: break;
-        }
-      }
-    }
-    // VALUE_HISTOGRAM: a row can hold tens of thousands of bins, so the workgroup's threads walk the bins of all keys
-    // (not one thread per key): every non-zero u32 bin becomes one u64 add into the global block
-    for (int a = 0; a < q->num_aggs; ++a) {
-      const DevAgg& A = q->aggs[a];
-      if (A.type != PA_AGG_VALUE_HISTOGRAM) continue;
-      const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off);
-      AS1 unsigned long long* g = gp((unsigned long long*)A.acc_i64);
-      for (int64_t i = threadIdx.x; i < K * A.nvals; i += WGS)
-        if (r[i] != 0) __hip_atomic_fetch_add(g + i, (unsigned long long)r[i], RLX);
-    }
-  }
+  if (is_pcount(STRAT)) pcount_store<WGS>(q, lds_acc, ps, lb);
+  if (is_pemit(STRAT)) pemit_finish<WGS>(q, lds_acc, ps, lb);
+  if (STRAT == STRAT_LDS) lds_acc_flush<WGS>(q, lds_acc);
 }
 
 // Kernel-pointer getters of the scan variants, one translation unit per group (parallel builds): nullptr when the
 // unit does not hold the strategy.
-const void* scan_fn_std(int strategy, int steps, int lm);   // pa_scan_std.hip: LDS, GLOBAL (LANE via scan_fn_lane)
-const void* scan_fn_lane(int strategy, int steps, int lm);  // pa_scan_lane.hip: LANE and its variants
+const void* scan_fn_std(int strategy, int steps, int lm);        // pa_scan_std.hip: STRAT_LDS
+const void* scan_fn_global(int strategy, int steps, int lm);     // pa_scan_global.hip: STRAT_GLOBAL
+const void* scan_fn_lane_lm(int strategy, int steps, int lm);    // pa_scan_lane_lm.hip: STRAT_LANE, _CNT, lane-major
+const void* scan_fn_lane_raw(int strategy, int steps, int lm);   // pa_scan_lane_raw.hip: STRAT_LANE_RAW (lane-major)
+const void* scan_fn_lane_dict(int strategy, int steps, int lm);  // pa_scan_lane_dict.hip: STRAT_LANE_DICT (lane-major)
+const void* scan_fn_lane_sm(int strategy, int steps, int lm);    // pa_scan_lane_sm.hip: STRAT_LANE, step-major
 const void* scan_fn_part_a(int strategy);                  // pa_scan_part_a.hip: PCOUNT + emit variants (one part)
 const void* scan_fn_part_b(int strategy);                  // pa_scan_part_b.hip: the other emit variants
 const void* scan_fn_part_mv(int strategy);                 // pa_scan_part_mv.hip: the multi-value group-by passes

@@ -82,6 +82,10 @@ def test_build_covers_every_source_and_rebuilds_objects_by_includes(monkeypatch)
     deps = {s: {os.path.basename(d) for d in B._deps(os.path.join(B.CSRC, s))} for s in B.SOURCES}
     assert "pa_host.h" in deps["pa_capi.hip"] and "pa_jit_abi.h" in deps["pa_jit.hip"]
     assert "pa_host.h" not in deps["pa_scan_std.hip"] and "pa_scan.h" in deps["pa_scan_std.hip"]
+    scan_units = [s for s in B.SOURCES if s.startswith("pa_scan_")]
+    assert len(scan_units) >= 11
+    for s in scan_units:  # every unit that instantiates scan kernels
+        assert "pa_scan.h" in deps[s] and "pa_host.h" not in deps[s], s
     t0 = 1_000_000.0
     real_exists = os.path.exists
 
