@@ -46,6 +46,11 @@
  *      fetched for every matching doc into a bounded priority queue), :193-322 (the rest of the row fetched for the
  *      rows kept) and operator/combine/SelectionOrderByCombineOperator.java (the segments' queues merged): one fused
  *      filter + top-K scan over every bound segment, then a select + sort of the candidates and a gather of the cells.
+ *  pa_query_set_distinct / pa_query_fetch_distinct
+ *      replace operator/query/DistinctOperator.java:55-84 with the dictionary-based executors
+ *      (query/distinct/dictionary/DictionaryBasedMultiColumnDistinct{Only,OrderBy}Executor.java) and
+ *      operator/combine/DistinctCombineOperator.java: one fused filter + key-presence bitmap scan over every bound
+ *      segment, then a rank / order pass over the bits.
  *  pa_query_accumulators / layout
  *      exposes the device accumulators so the cross-GPU merge of partial aggregates runs as an RCCL
  *      reduce (SUM for COUNT/SUM, MIN, MAX, MAX for HLL registers) — the multi-GPU analogue of
@@ -342,6 +347,41 @@ int pa_query_selection_segment_docs(const pa_query* q, int64_t* out);
  * (CAP). */
 int pa_query_selection_counters(const pa_query* q, int64_t* out);
 
+/* ---------------------------------------------------------------- distinct queries
+ * SELECT DISTINCT c1, c2, ... [WHERE filter] [ORDER BY ci [DESC], ...] [LIMIT n] (DistinctOperator +
+ * DistinctCombineOperator). The query is created from a GROUP BY spec without aggregations (num_aggs = 0): its group-by
+ * columns are the DISTINCT columns, with cardinalities and per-segment remaps bound as for GROUP BY, and it is turned
+ * into a distinct query before pa_query_prepare. The scan sets one bit per key of the direct key space
+ * (sum_j id_j * prod_{k<j} card_k) in the PA_ACC_KEYBITS_U32 section; the finish orders the present keys.
+ *
+ * Order: the ORDER BY entries first (each an index into the group-by columns, ascending or descending by table-wide
+ * value id), then every DISTINCT column not named, ascending, in select order: a total order of the keys, so the rows
+ * a limit keeps are a function of the data. Table-wide ids must therefore follow the order of the values.
+ *
+ * pa_query_prepare fails with PA_EUNSUPPORTED for raw (no-dictionary), multi-value and BYTES columns, for a key space
+ * of more than 2^31 keys, and for ORDER BY with limit > PA_MAX_SELECT_ROWS over a key space larger than that (a limit
+ * of the interface: the finish itself has no such bound). Without ORDER BY any limit >= 0 is accepted.
+ * When the order is not the key's own digit order (any ORDER BY but the single column ascending; two or more columns
+ * without ORDER BY) pa_query_prepare allocates a second bitmap of the key space's size (up to 256 MiB), which every
+ * fetch clears and fills. */
+typedef struct {
+  int32_t num_order_by;
+  int32_t order_by_index[PA_MAX_GROUP_BY];  /* index into the spec's group-by columns; each at most once */
+  int32_t order_by_desc[PA_MAX_GROUP_BY];   /* 1 = descending */
+  int64_t limit;
+} pa_distinct_spec;
+
+/* Before pa_query_prepare. pa_query_execute / reset / scan then drive the distinct scan; pa_query_fetch fails with
+ * PA_EINVAL on such a query (pa_query_fetch_distinct reads it, and like pa_query_fetch fails with PA_EINVAL while a
+ * tuning that skips work is set). */
+int pa_query_set_distinct(pa_query* q, const pa_distinct_spec* spec);
+
+/* The result of the last scan: min(limit, keys present) rows in final order, row-major in out_ids (int32[capacity *
+ * num_group_by]): one table-wide value id per DISTINCT column. *out_present (may be NULL) = distinct keys present,
+ * before the limit. Returns the number of rows (may exceed capacity: then only `capacity` were written), <0 on error;
+ * capacity = 0 only counts. Synchronises `stream`. */
+int64_t pa_query_fetch_distinct(pa_query* q, void* stream, int64_t capacity, int32_t* out_ids, int64_t* out_present);
+
 /* Tests and measurement only: overrides one planner decision of this query (the tunings, their ranges and defaults:
  * pinot_amd/csrc/pa_tuning.h; the library reads none of them from the environment). Before pa_query_prepare.
  * PA_EINVAL: unknown name, value outside the tuning's range, or query already prepared. */
@@ -382,6 +422,8 @@ int pa_query_scan(pa_query* q, void* stream);
 #define PA_ACC_HIST_U64 10 /* reduce SUM; VALUE_HISTOGRAM: [key * stride + value id] = times the group aggregated the
                               value, stride = num_values rounded up to a multiple of 2 (whole 16-byte units; a padding
                               bin stays 0). 64 bits: a GPU holds tens of billions of docs, so one bin can pass 2^32 */
+#define PA_ACC_KEYBITS_U32 11 /* reduce bitwise OR; distinct queries: bit (key & 31) of word (key >> 5) = the key is
+                                 present; the only per-key section of such a query (reset identity 0) */
 /* All sections live in one device block of pa_query_accumulator_bytes() bytes (256-byte aligned sections).
  * pa_query_set_accumulator_buffer lets the caller own that block (e.g. memory its collective library
  * registered) instead of the library: call after pa_query_prepare; `bytes` must be >= the size. */

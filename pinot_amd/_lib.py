@@ -53,7 +53,7 @@ PA_STATS_NON_SCAN, PA_STATS_HOST = -1, -2
 PA_BIT_AND, PA_BIT_OR, PA_BIT_NOT = -1, -2, -3
 PA_BIT_PROG_MAX = 64
 PA_ACC_COUNT_U64, PA_ACC_SUM_I64, PA_ACC_SUM_F64, PA_ACC_MIN_I64, PA_ACC_MAX_I64, PA_ACC_HLL_U8, \
-    PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64 = range(11)
+    PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64, PA_ACC_KEYBITS_U32 = range(12)
 PA_MAX_PERCENTILES = 64
 ABI_VERSION = 5
 
@@ -66,6 +66,7 @@ EXPORTED = [
     "pa_query_bind_value_remap", "pa_query_prepare", "pa_query_num_keys",
     "pa_query_set_selection", "pa_query_bind_order_remap", "pa_query_fetch_selection",
     "pa_query_selection_segment_docs", "pa_query_selection_counters",
+    "pa_query_set_distinct", "pa_query_fetch_distinct",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
     "pa_query_partition_keys",
@@ -126,6 +127,15 @@ class SelectSpec(ctypes.Structure):
     ]
 
 
+class DistinctSpec(ctypes.Structure):
+    _fields_ = [
+        ("num_order_by", ctypes.c_int32),
+        ("order_by_index", ctypes.c_int32 * PA_MAX_GROUP_BY),
+        ("order_by_desc", ctypes.c_int32 * PA_MAX_GROUP_BY),
+        ("limit", ctypes.c_int64),
+    ]
+
+
 class LeafParams(ctypes.Structure):
     _fields_ = [
         ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("negate", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -165,6 +175,8 @@ def _declare(lib):
         "pa_query_fetch_selection": (i64, [vp, vp, i64, vp, vp, vp, vp]),
         "pa_query_selection_segment_docs": (ctypes.c_int, [vp, vp]),
         "pa_query_selection_counters": (ctypes.c_int, [vp, vp]),
+        "pa_query_set_distinct": (ctypes.c_int, [vp, ctypes.POINTER(DistinctSpec)]),
+        "pa_query_fetch_distinct": (i64, [vp, vp, i64, vp, ctypes.POINTER(i64)]),
         "pa_query_prepare": (ctypes.c_int, [vp]),
         "pa_query_num_keys": (i64, [vp]),
         "pa_query_execute": (ctypes.c_int, [vp, vp]),

@@ -120,7 +120,7 @@ int pa_query_prepare(pa_query* q) {
   if (!rc) rc = plan_slots(q, P);
   if (!rc) rc = plan_key_space(q, P);
   if (!rc) rc = plan_limit(q, P);
-  if (!rc) rc = plan_gdense(q, P);
+  if (!rc && !q->is_distinct) rc = plan_gdense(q, P);  // (a distinct query has its own two strategies)
   if (!rc) rc = build_segments(q, P);
   if (!rc) rc = plan_walk(q, P);
   if (!rc) rc = plan_accumulators(q, P);
@@ -212,8 +212,12 @@ int pa_query_prepare(pa_query* q) {
   if (rc) return rc;
   rc = upload_descriptors(q);
   if (rc) return rc;
-  rc = jit_plan(q, P, cus);
+  if (!q->is_distinct) rc = jit_plan(q, P, cus);
   if (rc) return rc;
+  if (q->is_distinct) {
+    rc = distinct_plan(q);
+    if (rc) return rc;
+  }
   rc = pve_plan(q, P, cus);
   if (rc) return rc;
   PA_HIP(hipDeviceSynchronize());
@@ -387,6 +391,7 @@ int pa_query_set_accumulator_buffer(pa_query* q, void* device_buffer, uint64_t b
   auto relocate = [&](DevQuery& h) {
     h.count = (unsigned long long*)(nb + ((char*)h.count - old));
     h.matched_docs = (unsigned long long*)(nb + ((char*)h.matched_docs - old));
+    if (h.keybits) h.keybits = (uint32_t*)(nb + ((char*)h.keybits - old));
     if (q->hashed) h.ht_keys = (long long*)(nb + ((char*)h.ht_keys - old));
     for (int a = 0; a < h.num_aggs; ++a) {
       if (q->agg_section[a] < 0) continue;

@@ -56,8 +56,12 @@ enum Strategy : int32_t {
   STRAT_GDENSE_LM8 = 14, STRAT_GDENSE_LM16 = 15,
   // selection (SELECT columns ... ORDER BY ... LIMIT): filter + per-wave top-K candidates (pa_scan.h "selection");
   // its code lies above the emit variants' range (is_pemit)
-  STRAT_SELECT = 128
+  STRAT_SELECT = 128,
+  // distinct (SELECT DISTINCT ...): filter + one bit per key of the direct key space (pa_scan.h "distinct"): the
+  // workgroup-private LDS bitmap, flushed once per workgroup, or test-before-set on the bitmap in HBM
+  STRAT_DISTINCT_LDS = 129, STRAT_DISTINCT = 130
 };
+__host__ __device__ constexpr bool is_distinct(int s) { return s == STRAT_DISTINCT_LDS || s == STRAT_DISTINCT; }
 __host__ __device__ constexpr bool is_pcount(int s) { return s == STRAT_PCOUNT || s == STRAT_PCOUNT_MV; }
 // STRAT_GDENSE: 4-wave workgroups; STRAT_GDENSE8 / STRAT_GDENSE12: the same kernel with 8- / 12-wave workgroups (2 / 3
 // waves per SIMD when one workgroup fits a CU, e.g. beside a 64 KiB value table: the walk's LDS round trips and VALU
@@ -326,6 +330,7 @@ struct DevQuery {
   int64_t leap_cap;              // list entries per scan wave (E docs)
   int64_t leap_slices;           // scan waves (grid x waves per workgroup): one list slice each
   const struct SelDesc* sel;     // STRAT_SELECT: the selection's descriptor (nullptr otherwise)
+  uint32_t* keybits;             // distinct: the key-presence bitmap (PA_ACC_KEYBITS_U32), (num_keys + 31) / 32 words
 };
 // ---------------------------------------------------------------- selection (STRAT_SELECT)
 // One candidate of the top-K: (key, row) compared as one 128-bit unsigned number. key = the ORDER BY components,
@@ -369,6 +374,19 @@ struct SelDesc {
   SelEnt* sorted;            // finish: the result, ascending [next power of two >= K]
   int64_t* cells;            // finish: [nout][K] output cells
   uint32_t* result_n;        // finish: rows of the result
+};
+
+// ---------------------------------------------------------------- distinct (finish: pa_distinct.hip)
+// The completed order of a distinct query as the digits of a mixed-radix sort key, least significant first: digit i is
+// DISTINCT column col[i] (table-wide value id, or card - 1 - id when descending). The ORDER BY entries are the most
+// significant digits; the columns they do not name follow, ascending, in select order. A bijection of the raw key
+// (column 0 least significant), so sort keys are distinct and below num_keys.
+struct DstOrder {
+  int32_t n;                        // DISTINCT columns
+  int32_t col[PA_MAX_GROUP_BY];
+  int32_t card[PA_MAX_GROUP_BY];    // cardinality of col[i]
+  int32_t desc[PA_MAX_GROUP_BY];
+  int32_t kcard[PA_MAX_GROUP_BY];   // cardinalities by column: the raw key's digits
 };
 
 // STRAT_GDENSE per-segment parameter table: 64 dwords, loaded once per segment into ONE VGPR (lane k holds dword k)

@@ -13,6 +13,7 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
                        void* const* out_aggs) {
   if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
   if (q->is_select) return fail(PA_EINVAL, "a selection query has no groups: read it with pa_query_fetch_selection");
+  if (q->is_distinct) return fail(PA_EINVAL, "a distinct query has no groups: read it with pa_query_fetch_distinct");
   if (int rc = refuse_invalid(q)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const pa_query_spec& s = q->spec;

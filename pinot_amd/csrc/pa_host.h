@@ -139,6 +139,8 @@ constexpr int64_t kMinParts = 256;          // pass C parallelism: one workgroup
 constexpr int64_t kMaxParts = 4096;          // partitions of one query (both streams)
 constexpr int64_t kDirectMaxKeys = int64_t(1) << 27;  // direct-indexed key space limit (beyond: hashed keys)
 constexpr uint64_t kMaxHashSlots = uint64_t(1) << 28;
+// distinct queries: their own direct key space limit (one bit per key: a 256 MiB bitmap); no hashed form
+constexpr int64_t kDistinctMaxKeys = int64_t(1) << 31;
 constexpr uint64_t kWalkMaxBitmapBytes = uint64_t(4) << 30;  // numGroupsLimit walk: admitted-key bitmaps of a query
 constexpr size_t kLdsBudget = 160 * 1024;
 // pa_query_reset: accumulator blocks up to this size are reset by one kernel launch (reset_kernel), larger ones by
@@ -199,7 +201,9 @@ inline int64_t hist_stride(const pa_agg_spec& A) { return (A.num_values + 1) & ~
 // DISTINCTCOUNT and VALUE_HISTOGRAM index their accumulators by the column's table-wide value id
 inline bool value_id_agg(int32_t type) { return type == PA_AGG_DISTINCTCOUNT || type == PA_AGG_VALUE_HISTOGRAM; }
 // element bytes of an accumulator section
-inline size_t section_es(int32_t kind) { return (kind == PA_ACC_HLL_U8 || kind == PA_ACC_PRESENCE_U8) ? 1 : 8; }
+inline size_t section_es(int32_t kind) {
+  return (kind == PA_ACC_HLL_U8 || kind == PA_ACC_PRESENCE_U8) ? 1 : (kind == PA_ACC_KEYBITS_U32 ? 4 : 8);
+}
 
 struct pa_query {
   pa_query_spec spec;
@@ -322,8 +326,18 @@ struct pa_query {
   DevBuf sel_desc, sel_hdr, sel_scratch, sel_cand, sel_sorted, sel_cells;
   std::vector<int64_t> sel_seg_docs;  // read by the last pa_query_fetch_selection
   int64_t sel_counters[4] = {0, 0, 0, 0};
+  // distinct (pa_query_set_distinct; pa_distinct.hip): the spec, the completed order (DstOrder), whether it is the
+  // key's own digit order, and the finish buffers: per-block counts, the re-keyed bitmap, the output rows
+  bool is_distinct = false;
+  pa_distinct_spec dst_spec{};
+  DstOrder dst_order{};
+  bool dst_key_order = false;
+  DevBuf dst_counts, dst_bits2, dst_rows;
 
   ~pa_query() {
+    dev_free(dst_counts);
+    dev_free(dst_bits2);
+    dev_free(dst_rows);
     dev_free(sel_desc);
     dev_free(sel_hdr);
     dev_free(sel_scratch);
@@ -448,6 +462,9 @@ int alloc_leaps(pa_query* q, const Prep& P);
 int select_validate(pa_query* q);               // prepare: the selection's columns and key against the bound segments
 int select_plan(pa_query* q);                   // prepare, once the grid is known: caps it, allocates, fills hq.sel
 int select_reset(pa_query* q, hipStream_t st);  // pa_query_reset
+// pa_distinct.hip
+int distinct_key_space(pa_query* q, Prep& P);   // prepare (plan_key_space): columns, the direct key space, the order
+int distinct_plan(pa_query* q);                 // prepare, last: the finish buffers
 // pa_jit.hip
 int jit_plan(pa_query* q, const Prep& P, int cus);
 void jit_fill_pointers(pa_query* q, JitArgs& a);

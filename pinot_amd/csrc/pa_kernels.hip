@@ -1874,6 +1874,11 @@ hipError_t launch_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_scan_u64(uint64_t* v, int64_t n, hipStream_t s) {
+  scan_u64_kernel<<<1, 256, 0, s>>>(v, n);
+  return hipGetLastError();
+}
+
 hipError_t launch_reset(const ResetArgs& a, hipStream_t s) {
   reset_kernel<<<grid_for(a.block_words + a.header_words, 256), 256, 0, s>>>(a);
   return hipGetLastError();
@@ -1967,6 +1972,7 @@ static const void* scan_fn(int strategy, int steps, int lm) {
     if (const void* f = get(strategy, steps, lm)) return f;
   if (const void* f = scan_fn_gdense(strategy, lm)) return f;
   if (const void* f = scan_fn_select(strategy, steps)) return f;
+  if (const void* f = scan_fn_distinct(strategy, steps)) return f;
   if (const void* f = scan_fn_part_a(strategy)) return f;
   if (const void* f = scan_fn_part_mv(strategy)) return f;
   return scan_fn_part_b(strategy);

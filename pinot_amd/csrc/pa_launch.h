@@ -95,6 +95,8 @@ hipError_t launch_hll_lut_numeric(const int64_t* di, const double* dd, int32_t v
                                   uint32_t* lut, hipStream_t s);
 hipError_t launch_hll_lut_hashes(const int32_t* hashes, int32_t card, int32_t log2m, uint32_t* lut, hipStream_t s);
 hipError_t launch_fill_i64(int64_t* p, int64_t n, int64_t v, hipStream_t s);
+// in-place exclusive scan of n 64-bit counts by one workgroup; v[n] = total (scan_u64_kernel)
+hipError_t launch_scan_u64(uint64_t* v, int64_t n, hipStream_t s);
 // pa_query_reset as one launch: the accumulator block and the leap header to zero, except the block's MIN / MAX / KEYS
 // sections, which take their identities (every range in 8-byte words; the table travels by value)
 struct ResetArgs {

@@ -244,6 +244,7 @@ int plan_slots(pa_query* q, Prep& P) {
 // 64-bit key, mapped to an accumulator slot by a global open-addressing table (the IntMap / LongMap /
 // NoDictionary*GroupKeyGenerator holders of the reference).
 int plan_key_space(pa_query* q, Prep& P) {
+  if (q->is_distinct) return distinct_key_space(q, P);  // (its own bound, direct only)
   const pa_query_spec& s = q->spec;
   q->hashed = false;
   q->key_words = 1;
@@ -974,7 +975,9 @@ int plan_accumulators(pa_query* q, Prep& P) {
   q->sections.clear();
   q->agg_section.assign(s.num_aggs, -1);
   std::vector<std::pair<int32_t, int64_t>> sec;  // kind, elements
-  sec.push_back({PA_ACC_COUNT_U64, K});
+  // (a distinct query's only per-key section is the key-presence bitmap)
+  if (q->is_distinct) sec.push_back({PA_ACC_KEYBITS_U32, (K + 31) / 32});
+  else sec.push_back({PA_ACC_COUNT_U64, K});
   for (int a = 0; a < s.num_aggs; ++a) {
     const pa_agg_spec& A = s.aggs[a];
     switch (A.type) {
@@ -1017,7 +1020,8 @@ int plan_accumulators(pa_query* q, Prep& P) {
   for (size_t i = 0; i < sec.size(); ++i)
     q->sections.push_back({sec[i].first, (char*)q->acc.p + offs[i], sec[i].second});
   // LDS strategy layout: u32 counts, then every aggregation's WG-private accumulators
-  P.lds_acc = ((size_t)K * 4 + 15) & ~(size_t)15;
+  // (distinct: the workgroup's bitmap)
+  P.lds_acc = q->is_distinct ? ((size_t)((K + 31) / 32) * 4 + 15) & ~(size_t)15 : ((size_t)K * 4 + 15) & ~(size_t)15;
   P.agg_lds.assign(s.num_aggs, 0);
   for (int a = 0; a < s.num_aggs; ++a) {
     const pa_agg_spec& A = s.aggs[a];

@@ -460,6 +460,32 @@ int plan_kernels(pa_query* q, Prep& P, TilePlan& plan, TilePlan& count_plan) {
     q->dma_slots = plan.dma;
     return PA_OK;
   }
+  if (q->is_distinct) {
+    // Distinct: the step-major scan with the key-presence bitmap. The workgroup-private LDS bitmap when its words fit in
+    // front of the tile rings (plan_tiles: the LDS budget and the occupancy the compiled kernel really has) and leave as
+    // many workgroups resident per CU as the plan without it has; else test-before-set on the bitmap in HBM, whose LDS
+    // goes to the rings. (Measured, DESIGN section 5: a 128 KiB bitmap at one workgroup per CU takes twice the time of
+    // the global bitmap at four; tuning distinct_lds = 2 takes the LDS bitmap whenever it fits.)
+    q->partitioned = false;
+    P.lm = false;
+    const TilePlan gplan = plan_tiles(q, q->hsegs, STRAT_DISTINCT, false, 0, false);
+    plan = TilePlan{};
+    if (q->tune.distinct_lds != 0 && P.lds_acc < kLdsBudget)
+      plan = plan_tiles(q, q->hsegs, STRAT_DISTINCT_LDS, false, P.lds_acc, false);
+    if (plan.score >= 0 && (q->tune.distinct_lds == 2 || plan.wg_per_cu >= gplan.wg_per_cu)) {
+      q->strategy = STRAT_DISTINCT_LDS;
+    } else {
+      q->strategy = STRAT_DISTINCT;
+      P.lds_acc = 0;
+      plan = gplan;
+    }
+    if (plan.score < 0) return fail(PA_EUNSUPPORTED, "staged columns too wide for the LDS tile ring");
+    PLAN_LOG("distinct: K=%lld %s bitmap", (long long)K, q->strategy == STRAT_DISTINCT_LDS ? "LDS" : "global");
+    q->lds_bytes = (int)plan.lds;
+    q->steps = plan.steps;
+    q->dma_slots = plan.dma;
+    return PA_OK;
+  }
   // Lane-major kernel: every eager literal is a dictionary leaf on a staged column and the per-segment plan table
   // has room for the staged columns and eager literals (otherwise the step-major kernel runs the query).
   bool lm = !(s.flags & (PA_QF_NO_LANE_MAJOR | PA_QF_STEPS16)) && q->num_eager <= kLmEager;
@@ -785,7 +811,9 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
   for (int li = 0; li < PA_MAX_LEAVES; ++li) h.gd_lut[li] = -1;
   h.xcd_major = (P.dense || is_gdense(q->strategy)) ? 1 : 0;
   h.lds_count_off = 0;
-  h.lds_acc_bytes = (q->strategy == STRAT_LDS || is_gdense(q->strategy) || is_lane(q->strategy) || q->strategy == STRAT_SELECT)
+  h.keybits = q->is_distinct ? (uint32_t*)q->sections[0].ptr : nullptr;
+  h.lds_acc_bytes = (q->strategy == STRAT_LDS || is_gdense(q->strategy) || is_lane(q->strategy) || q->strategy == STRAT_SELECT ||
+                     q->strategy == STRAT_DISTINCT_LDS)
                         ? (uint32_t)P.lds_acc : 0;
   if (is_gdense(q->strategy)) {
     // per-segment parameter tables (GdSegPlan): the query's key box and LDS layout + the segment's staged regions

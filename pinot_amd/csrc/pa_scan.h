@@ -203,6 +203,7 @@ __device__ __forceinline__ int64_t xcd_major_block(int64_t b, int64_t G) {
 //   leap_slice                     every strategy: the wave's index in logical (XCD-major) block order
 //   leap_n, leap_lds               every strategy with DevQuery::leap_mode (leap_tile)
 //   sel_*                          STRAT_SELECT, set by sel_state_init
+// (the distinct strategies keep no per-wave state: their bitmap is the workgroup's or global)
 struct WaveState {
   // Per-thread slots in LDS (the workgroup's lane-accumulator area at the front of the dynamic LDS: kLaneAccBytes per
   // thread and aggregation), so no accumulator occupies a VGPR across the tile loop: aggregation a of thread t keeps
@@ -3001,6 +3002,119 @@ __device__ __forceinline__ void sel_counters_flush(const DevQuery* q, const Wave
   }
 }
 
+// ---------------------------------------------------------------- distinct (STRAT_DISTINCT_LDS / STRAT_DISTINCT)
+// SELECT DISTINCT c1, c2, ...: the accumulator is a set of keys, one bit per key of the direct key space (bit key & 31
+// of word key >> 5, DevQuery::keybits; DistinctOperator.java:55-84 offers every matching doc's record to a set). Keys
+// are below 2^31 (kDistinctMaxKeys), so all key arithmetic is 32-bit.
+//   STRAT_DISTINCT_LDS: a workgroup-private bitmap in LDS in front of the tile rings, zeroed in the prologue; a matching
+//     doc is one no-return LDS OR; the epilogue ORs the non-zero words into the bitmap in HBM.
+//   STRAT_DISTINCT: the bitmap in HBM. A plain load of the key's word comes first and the relaxed OR is issued only
+//     when the bit is not yet set: a stale 0 costs a redundant atomic, and a 1 is never stale, because bits are only
+//     set between two resets. Batches of 8 steps: every key of the batch, then every word load, then the atomics, so
+//     one wait behind the ring's in-flight DMA (vmcnt counts in order) covers 8 loads per lane.
+// In both, when every active lane of a step has its key in one word (a hot key, a key range inside one word), the
+// lanes combine their bits and one of them updates (dst_combine); otherwise every lane updates on its own. Grouping the
+// lanes word by word, as accumulate_step groups equal keys, was measured and dropped: with a few lanes spread over a
+// few words per step it ran one ballot + shuffle pass per word and took 0.71 of 1.52 ms of the scan.
+// Measurement only (tuning debug_emit, results invalid; DESIGN section 5 takes the scan apart with them): bit 0 skips the
+// atomics, bit 1 also the global variant's word loads, bit 2 the in-wave combining (every lane goes on its own), bit 3
+// the global variant's word load only (a plain atomic per doc: no test-before-set).
+constexpr int kDstDbgNoAtomic = 1, kDstDbgNoLoad = 2, kDstDbgNoCombine = 4, kDstDbgPlainAtomic = 8;
+__device__ __forceinline__ uint32_t distinct_key(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                                 const uint32_t* img, int doc_local, int64_t doc) {
+  uint32_t key = 0;
+  for (int j = 0; j < q->num_gb; ++j)
+    key += (uint32_t)gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc) * (uint32_t)q->gb_stride[j];
+  return key;
+}
+
+// One step's active lanes: true for the lanes that update the bitmap, with `bit` the OR of the bits of every lane they
+// stand for: the first active lane for all of them when they share one word, else every active lane for itself.
+__device__ __forceinline__ bool dst_combine(uint32_t word, uint32_t& bit, bool act, int lane) {
+  const uint64_t active = __ballot(act);
+  if (active == 0) return false;
+  const int leader = __builtin_ctzll(active);
+  const uint32_t w0 = (uint32_t)__shfl((int)word, leader);
+  if (__ballot(act && word == w0) != active) return act;
+  uint32_t b = act ? bit : 0u;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) b |= (uint32_t)__shfl_xor((int)b, o);
+  if (lane == leader) bit = b;
+  return lane == leader;
+}
+
+// The docs of one tile that passed the filter (bit i of m: the lane's doc of step i) into the bitmap.
+template <int STRAT, int STEPS, int LM>
+__device__ __forceinline__ void distinct_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                              const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
+                                              unsigned char* lds) {
+  auto local = [&](int i) { return LM ? 32 * lane + i : i * kWave + lane; };
+  const int dbg = q->debug_emit;
+  if constexpr (STRAT == STRAT_DISTINCT_LDS) {
+    lds_u32_t* bm = lds_ptr(lds);
+    for (int i = 0; i < STEPS; ++i) {
+      const bool act = ((m >> i) & 1u) != 0;
+      if (__ballot(act) == 0) continue;
+      const uint32_t key = act ? distinct_key(q, seg, img, local(i), doc_base + local(i)) : 0u;
+      uint32_t bit = 1u << (key & 31u);
+      const bool issue = (dbg & kDstDbgNoCombine) ? act : dst_combine(key >> 5, bit, act, lane);
+      if (dbg & kDstDbgNoAtomic) asm volatile("" ::"v"(bit), "v"(key));
+      else if (issue) __hip_atomic_fetch_or(bm + (key >> 5), bit, WG_RLX);
+    }
+  } else {
+    AS1 uint32_t* bm = gp(q->keybits);
+    constexpr int B = 8;
+    static_assert(STEPS % B == 0, "whole batches");
+    for (int i0 = 0; i0 < STEPS; i0 += B) {
+      const uint32_t mm = (m >> i0) & ((1u << B) - 1u);
+      if (__ballot(mm != 0) == 0) continue;
+      uint32_t word[B], bit[B], old[B];
+      uint32_t iss = 0;
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        const bool act = ((mm >> b) & 1u) != 0;
+        const uint32_t key = act ? distinct_key(q, seg, img, local(i0 + b), doc_base + local(i0 + b)) : 0u;
+        word[b] = key >> 5;
+        bit[b] = 1u << (key & 31u);
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        if (dbg & kDstDbgNoCombine) iss |= mm & (1u << b);
+        else if (__ballot((mm >> b) & 1u) != 0 && dst_combine(word[b], bit[b], ((mm >> b) & 1u) != 0, lane)) iss |= 1u << b;
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+        old[b] = !((iss >> b) & 1u) ? ~0u : ((dbg & (kDstDbgNoLoad | kDstDbgPlainAtomic)) ? 0u : bm[word[b]]);
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        if (dbg & kDstDbgNoAtomic) asm volatile("" ::"v"(old[b]), "v"(bit[b]), "v"(word[b]));
+        else if ((bit[b] & ~old[b]) != 0) __hip_atomic_fetch_or(bm + word[b], bit[b], RLX);
+      }
+    }
+  }
+}
+
+// STRAT_DISTINCT_LDS, start of the kernel: the workgroup's bitmap to zero.
+template <int WGS>
+__device__ __forceinline__ void distinct_lds_zero(const DevQuery* q, unsigned char* lds) {
+  lds_u32_t* bm = lds_ptr(lds);
+  const uint32_t words = (uint32_t)((q->num_keys + 31) >> 5);
+  for (uint32_t w = threadIdx.x; w < words; w += WGS) bm[w] = 0u;
+  __syncthreads();
+}
+
+// STRAT_DISTINCT_LDS, end of the kernel: one global OR per non-zero word.
+template <int WGS>
+__device__ __forceinline__ void distinct_lds_flush(const DevQuery* q, unsigned char* lds) {
+  __syncthreads();
+  const lds_u32_t* bm = lds_ptr(lds);
+  const uint32_t words = (uint32_t)((q->num_keys + 31) >> 5);
+  for (uint32_t w = threadIdx.x; w < words; w += WGS) {
+    const uint32_t v = bm[w];
+    if (v != 0u) __hip_atomic_fetch_or(gp(q->keybits) + w, v, RLX);
+  }
+}
+
 // The rare part of a tile (some doc survived the eager clauses): lazy clauses per surviving doc, then aggregation.
 // Returns the docs that matched.
 // LM: doc of bit i of lane l = 32l + i (lane-major tile), else 64i + l.
@@ -3046,6 +3160,8 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
   }
   if constexpr (STRAT == STRAT_SELECT) {
     select_tile<STEPS, LM>(q, seg, img, doc_base, m, lane, la);
+  } else if constexpr (is_distinct(STRAT)) {
+    distinct_tile<STRAT, STEPS, LM>(q, seg, img, doc_base, m, lane, lds);
   } else if constexpr (is_lane(STRAT)) {
     if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_tile<LM, STEPS, STRAT>(q, seg, img, doc_base, m, lane, la, lds);
   } else if constexpr (is_pcount(STRAT) || is_pemit(STRAT)) {
@@ -3376,6 +3492,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
                 (uint32_t)wave * (uint32_t)q->leap_lds_cap * 8u;
   if constexpr (is_lane(STRAT) && STRAT != STRAT_LANE_CNT) lane_acc_init(q, la, smem, WGS);
   if constexpr (STRAT == STRAT_SELECT) sel_state_init(la, smem, wave);
+  if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_zero<WGS>(q, lds_acc);
   const int64_t T = q->total_wtiles;
   const int64_t W = (int64_t)gridDim.x * WPW;
@@ -3529,6 +3646,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
       if (lane == 0) gp(q->leap_out)[3 * (int64_t)q->num_segments + 1 + la.leap_slice] = la.leap_n;
     }
   if constexpr (STRAT == STRAT_SELECT) sel_counters_flush(q, la, lane);
+  if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_flush<WGS>(q, lds_acc);
   if (!is_pemit(STRAT)) {  // (the partitioned count pass counts numDocsScanned; its emit pass sees the same docs)
     const int64_t wm = wave_sum_i64((int64_t)matched);
     if (lane == 0 && wm != 0) __hip_atomic_fetch_add(gp(q->matched_docs), (unsigned long long)wm, RLX);
@@ -3556,5 +3674,6 @@ const void* scan_fn_part_b(int strategy);                  // pa_scan_part_b.hip
 const void* scan_fn_part_mv(int strategy);                 // pa_scan_part_mv.hip: the multi-value group-by passes
 const void* scan_fn_gdense(int strategy, int lm);          // pa_scan_gdense.hip: STRAT_GDENSE (pa_gdense.h)
 const void* scan_fn_select(int strategy, int steps);       // pa_scan_select.hip: STRAT_SELECT (step-major tiles)
+const void* scan_fn_distinct(int strategy, int steps);     // pa_scan_distinct.hip: STRAT_DISTINCT* (step-major tiles)
 
 }  // namespace pa

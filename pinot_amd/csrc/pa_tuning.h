@@ -68,7 +68,10 @@
   X(select_scratch_mib, 256, 1, 16384, 0)                                                                              \
   /* selection: candidates per scan wave (CAP), K + 1 .. max(2 K, 128) (checked at prepare; default: that maximum).    \
      A small CAP makes small tables reach the in-place compaction */                                                  \
-  X(select_cap, -1, 2, 131072, 0)
+  X(select_cap, -1, 2, 131072, 0)                                                                                      \
+  /* distinct (STRAT_DISTINCT_LDS): 0 = never the workgroup-private LDS bitmap, 1 = the planner's choice (default:    \
+     the LDS bitmap when it fits next to the tile ring without costing resident workgroups), 2 = whenever it fits */   \
+  X(distinct_lds, 1, 0, 2, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;

@@ -465,7 +465,7 @@ class GpuQueryExecutor:
                 if gd is None or d is gd or (len(d) == len(gd) and np.array_equal(d, gd)):
                     rm.append(None)
                 else:
-                    rm.append(np.searchsorted(gd, d).astype(np.int32))
+                    rm.append(self._group_remap(name, gd, d))
             self.remaps.append(rm)
         spec.flags = ((self.flags & 0xffffffff) ^ 0x80000000) - 0x80000000  # (int32: PA_QF_NO_JIT is bit 31)
         spec.flags2 = (self.flags >> 32) & 0x7fffffff if self.flags >= 0 else 0
@@ -535,6 +535,11 @@ class GpuQueryExecutor:
             self.strides.append(s)
             s *= len(gd) if gd is not None else 1
 
+    def _group_remap(self, name, table_dict, dictionary):
+        """int32[len(dictionary)]: the table-wide key id of every value of a segment's dictionary of group-by column
+        `name` (both ascending in numpy's order here; DistinctExecutor orders STRING columns as the reference does)."""
+        return np.searchsorted(table_dict, dictionary).astype(np.int32)
+
     def _after_create(self):
         """Between pa_query_create and the first pa_query_bind_segment (SelectionExecutor sets the selection here)."""
 
@@ -584,7 +589,8 @@ class GpuQueryExecutor:
         code = out["plan"]["strategy"]
         out["plan"]["strategy"] = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane", 6: "lane", 7: "lane",
                                     8: "lds_dense", 9: "lds_dense", 10: "lds_dense", 11: "lds_dense", 12: "lds_dense",
-                                    14: "lds_dense", 15: "lds_dense", 128: "select"}[code]
+                                    14: "lds_dense", 15: "lds_dense", 128: "select", 129: "distinct",
+                                    130: "distinct"}[code]
         out["plan"]["variant"] = STRATEGY_VARIANTS.get(code, str(code))
         out["plan"]["eager_literals"] = int(L.lib().pa_query_num_eager_literals(self.handle))
         out["plan"]["lane_major"] = int(L.lib().pa_query_lane_major(self.handle))
@@ -903,7 +909,7 @@ class GpuQueryExecutor:
 # the kernel variant behind each pa_query_plan strategy code (pa_device.h Strategy)
 STRATEGY_VARIANTS = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane_cnt", 6: "lane_raw", 7: "lane_dict",
                      8: "gdense4", 9: "gdense8", 10: "gdense12", 11: "gdense_rs12", 12: "gdense_rs8", 14: "gdense_lm8",
-                     15: "gdense_lm16", 128: "select"}
+                     15: "gdense_lm16", 128: "select", 129: "distinct_lds", 130: "distinct_global"}
 
 
 class SelectionExecutor(GpuQueryExecutor):
@@ -1066,6 +1072,124 @@ class SelectionExecutor(GpuQueryExecutor):
     def run(self, stream=None):
         if self.handle is not None:
             self.execute(stream)
+        return self.fetch(stream)
+
+
+class DistinctExecutor(GpuQueryExecutor):
+    """SELECT DISTINCT c1, c2, ... [WHERE ...] [ORDER BY ci [DESC], ...] [LIMIT n] over the segments of one GPU:
+    DistinctOperator on every segment + DistinctCombineOperator, as one fused filter + key-presence bitmap scan and a
+    rank pass over the bits (include/pinot_amd.h "distinct queries"). The rows come back under the completed order
+    (distinct.completed_order), so which records a limit keeps is a function of the data.
+
+    table_dicts: optional {DISTINCT column: values ascending in the column's order (selection.table_order_dictionary)}
+    — the table-wide dictionary whose ids the keys hold; by default the union of these segments' dictionaries.
+    force_scan: run the GPU scan even where the reference answers from the dictionary (one dictionary column, no
+    filter); the rows are the same."""
+
+    def __init__(self, query: Q.Query, gpu_segments: List[GpuSegment], flags=0, table_dicts=None, tuning=None,
+                 force_scan=False):
+        from . import distinct as D
+        from . import selection as S
+        if not query.is_distinct:
+            raise ValueError("not a distinct query")
+        if not gpu_segments:
+            raise ValueError("no segments")
+        if str(query.options.get("enableNullHandling", "false")).lower() == "true":
+            raise UnsupportedQuery("distinct with null handling")
+        self.distinct = query
+        self.result_columns = list(query.select_columns)
+        if len(set(self.result_columns)) != len(self.result_columns):
+            raise UnsupportedQuery("a column appears twice in the DISTINCT list")
+        if len(self.result_columns) > L.PA_MAX_GROUP_BY:
+            raise UnsupportedQuery("too many DISTINCT columns")
+        seg0 = gpu_segments[0].segment
+        for c in self.result_columns:
+            if c not in seg0.columns:
+                raise UnsupportedQuery("transform expression or unknown column in the DISTINCT list: %r" % (c,))
+        self.result_types = [seg0.column(c).data_type for c in self.result_columns]
+        self.order = D.completed_order(query)
+        self.total_docs = sum(g.segment.num_docs for g in gpu_segments)
+        bound = [g.segment for g in gpu_segments if g.segment.num_docs > 0]
+        # table-wide dictionaries in the reference's value order (STRING: UTF-16 code units, not numpy's code points)
+        dicts = dict(table_dicts or {})
+        for c, dt in zip(self.result_columns, self.result_types):
+            if c not in dicts and bound and all(s.column(c).has_dictionary for s in bound):
+                ds = [s.column(c).dictionary for s in bound]
+                if dt == "STRING" or any(d is not ds[0] and not (len(d) == len(ds[0]) and np.array_equal(d, ds[0]))
+                                         for d in ds):
+                    dicts[c] = S.table_order_dictionary(ds, dt)[0]
+        self.fast_path = bool(bound) and not force_scan and D.dictionary_fast_path(query, [g.segment for g in gpu_segments])
+        group = dataclasses.replace(query, aggregations=[], aliases=[], group_by=list(self.result_columns), order_by=[],
+                                    select_columns=[], num_select_aggs=0, distinct=False, limit=10, offset=0)
+        if not bound or self.fast_path:  # nothing to scan, or answered from the dictionary: no plan, no launch
+            self.query, self.handle, self.placeholder, self.segs, self.gsegs = group, None, None, bound, []
+            self.all_segs = [g.segment for g in gpu_segments]
+            self.match_none = False
+            self.table_dicts = dicts
+            return
+        try:
+            super().__init__(group, gpu_segments, flags=flags, enforce_num_groups_limit=False, table_dicts=dicts,
+                             tuning=tuning)
+        except L.PinotAmdError as e:
+            if "(%d)" % -4 in str(e) and not isinstance(e, UnsupportedQuery):  # PA_EUNSUPPORTED
+                raise UnsupportedQuery(str(e))
+            raise
+
+    def _group_remap(self, name, table_dict, dictionary):
+        from . import selection as S
+        dt = self.result_types[self.result_columns.index(name)]
+        return S.order_remap(S.order_keys(table_dict, dt), dictionary, dt)
+
+    def _after_create(self):
+        spec = L.DistinctSpec()
+        named = [(j, asc) for j, asc in self.order[:len({o.expr for o in self.distinct.order_by})]]
+        spec.num_order_by = len(named)
+        for i, (j, asc) in enumerate(named):
+            spec.order_by_index[i] = j
+            spec.order_by_desc[i] = 0 if asc else 1
+        spec.limit = int(self.distinct.limit)
+        L.check(L.lib().pa_query_set_distinct(self.handle, ctypes.byref(spec)), "pa_query_set_distinct")
+
+    def fetch(self, stream=None, execution_stats=True):
+        """The DistinctResult of the last scan (synchronises `stream`)."""
+        from . import distinct as D
+        q = self.distinct
+        if self.fast_path:
+            return D.dictionary_distinct(q, self.all_segs)
+        res = D.DistinctResult(list(self.result_columns), list(self.result_types), num_total_docs=self.total_docs)
+        if self.handle is None or self.match_none:  # no docs at all / EmptyFilterOperator: nothing read
+            res.num_docs_scanned = res.num_entries_scanned_in_filter = res.num_entries_scanned_post_filter = 0
+            return res
+        lib = L.lib()
+        ncol = len(self.result_columns)
+        present = ctypes.c_int64()
+        cap = min(int(q.limit), self.num_keys, sum(s.num_docs for s in self.segs))
+        if cap > 1 << 20:  # a capacity-0 call only counts, so the rows are copied once, at the exact size
+            cap = L.check(lib.pa_query_fetch_distinct(self.handle, stream, 0, None, ctypes.byref(present)),
+                          "pa_query_fetch_distinct")
+        ids = OUTPUT_POOL.array("distinct_ids", max(1, cap * ncol), np.int32)
+        n = L.check(lib.pa_query_fetch_distinct(self.handle, stream, cap, ids.ctypes.data, ctypes.byref(present)),
+                    "pa_query_fetch_distinct")
+        n = min(n, cap)
+        ids = ids[:n * ncol].reshape(n, ncol)
+        cols = [np.asarray(self.global_dicts[j])[ids[:, j]].tolist() for j in range(ncol)]
+        res.rows = [list(r) for r in zip(*cols)]
+        res.present = int(present.value)
+        # exact with ORDER BY (every matching doc is offered), or when the limit was not reached (no early termination)
+        if q.order_by or res.present < int(q.limit):
+            matched = int(lib.pa_query_matched_docs(self.handle))
+            res.num_docs_scanned = matched
+            res.num_entries_scanned_post_filter = matched * ncol
+            if execution_stats:
+                res.num_entries_scanned_in_filter = self.execution_stats(stream, matched)[0]
+        return res
+
+    def execute(self, stream=None):
+        if self.handle is not None:
+            super().execute(stream)
+
+    def run(self, stream=None):
+        self.execute(stream)
         return self.fetch(stream)
 
 

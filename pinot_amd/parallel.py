@@ -490,6 +490,10 @@ class DistributedAccumulators:
 
     def __init__(self, executor, device):
         hashed = getattr(executor, "hashed", False)
+        if getattr(executor, "distinct", None) is not None:
+            # (before any collective: every rank holds the same kind of executor)
+            raise L.PinotAmdError("a distinct query is not reduced element-wise (RCCL has no bitwise-OR reduction and the "
+                                  "rows are few): fetch every rank's DistinctResult and merge with gather_distinct")
         if dist.is_initialized():
             # the collective first, on every rank (a hashed rank, or one holding only empty segments and built without the
             # layout's schema, joins with -1 and every rank then raises)
@@ -565,3 +569,14 @@ def gather_selection(result, query, group=None):
     parts = [None] * world
     dist.all_gather_object(parts, result, group=group)
     return merge_selection(parts, query)
+
+
+def gather_distinct(result, query, group=None):
+    """Every rank's DistinctResult (engine.DistinctExecutor.fetch) to every rank, merged as the broker merges servers
+    (reduce.merge_distinct). The rows are few (at most `limit` per rank), so they travel as objects: no collective
+    kernel. Returns (column names, rows), the same on every rank."""
+    from .reduce import merge_distinct
+    world = dist.get_world_size(group)
+    parts = [None] * world
+    dist.all_gather_object(parts, result, group=group)
+    return merge_distinct(parts, query)

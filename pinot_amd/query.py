@@ -5,6 +5,8 @@ parser for the SQL subset the reference's query tests use on this path:
   [LIMIT n] [OPTION(k=v, ...)]
   SELECT col, ... | * FROM t [WHERE filter] [ORDER BY c1 [ASC|DESC], ...] [LIMIT [offset,] n | LIMIT n OFFSET m]
   (a selection: Query.is_selection; SelectionOnlyOperator / SelectionOrderByOperator on the server)
+  SELECT DISTINCT c1, c2, ... | DISTINCT(c) FROM t [WHERE filter] [ORDER BY ci [ASC|DESC], ...] [LIMIT n]
+  (Query.is_distinct; DistinctOperator on the server. ORDER BY columns must be among the DISTINCT columns)
 
 filter: AND / OR / NOT / ( ) over  col = v | col != v | col <> v | col < v | col <= v | col > v | col >= v |
         col BETWEEN a AND b | col IN (...) | col NOT IN (...) | REGEXP_LIKE(col, 'regex') | col [NOT] LIKE 'pattern'
@@ -225,11 +227,18 @@ class Query:
     num_select_aggs: int = -1   # aggregations after this index are ORDER BY-only
     offset: int = 0             # LIMIT offset, n / LIMIT n OFFSET offset (selections: the broker drops these rows)
     select_star: bool = False   # SELECT *: every physical column of the schema
+    distinct: bool = False      # SELECT DISTINCT select_columns (QueryContextUtils.isDistinctQuery)
 
     @property
     def is_selection(self):
-        """No aggregation and no GROUP BY: SELECT columns / * [ORDER BY ...] (QueryContextUtils.isSelectionQuery)."""
-        return not self.aggregations and not self.group_by
+        """No aggregation, no GROUP BY, no DISTINCT: SELECT columns / * [ORDER BY ...]
+        (QueryContextUtils.isSelectionQuery)."""
+        return not self.aggregations and not self.group_by and not self.distinct
+
+    @property
+    def is_distinct(self):
+        """SELECT DISTINCT columns: neither a selection nor an aggregation."""
+        return bool(self.distinct)
 
     @property
     def num_groups_limit(self):
@@ -244,7 +253,7 @@ class Query:
         for a in self.aggregations:
             if a.column:
                 cols.add(a.column)
-        if self.is_selection:
+        if self.is_selection or self.is_distinct:
             cols.update(self.select_columns)
             cols.update(o.expr for o in self.order_by if isinstance(o.expr, str))
 
@@ -466,8 +475,13 @@ class _Parser:
         self.expect_kw("SELECT")
         aggs, aliases, plain_cols = [], [], []
         star = False
+        # SELECT DISTINCT c1, c2 / SELECT DISTINCT(c): the DISTINCT columns are the select list
+        distinct = self.kw("DISTINCT")
+        paren = distinct and self.op("(")
         while True:
             tok, nxt = self.peek(), self.peek(1)
+            if distinct and (tok[0] != "id" or (nxt[0] == "op" and nxt[1] == "(")):
+                raise ValueError("DISTINCT takes plain columns (no aggregations, no *): %r" % (tok,))
             if self.op("*"):
                 star = True
             elif tok[0] == "id" and not (nxt[0] == "op" and nxt[1] == "("):
@@ -477,9 +491,15 @@ class _Parser:
                 aliases.append(self.ident() if self.kw("AS") else None)
             if not self.op(","):
                 break
+        if paren:
+            if len(plain_cols) != 1:
+                raise ValueError("DISTINCT(c) takes one column; write several as SELECT DISTINCT c1, c2")
+            self.expect_op(")")
+            if self.op(","):
+                raise ValueError("DISTINCT(...) is the whole select list: no aggregation or column may follow it")
         self.expect_kw("FROM")
         self.ident()
-        q = Query(aggregations=aggs, aliases=aliases)
+        q = Query(aggregations=aggs, aliases=aliases, distinct=distinct)
         q.select_columns = plain_cols
         q.num_select_aggs = len(aggs)
         q.select_star = star
@@ -538,6 +558,14 @@ class _Parser:
             self.expect_op(")")
         if self.peek()[0] is not None:
             raise ValueError("trailing tokens: %r" % (self.t[self.i:],))
+        if distinct:
+            # (the reference: "ORDER-BY columns should be included in the DISTINCT columns", and no aggregation or
+            # GROUP BY next to DISTINCT; DistinctExecutorFactory looks ORDER BY expressions up in the DISTINCT list)
+            if aggs or q.group_by:
+                raise ValueError("DISTINCT next to aggregations or GROUP BY")
+            for o in q.order_by:
+                if o.expr not in plain_cols:
+                    raise ValueError("ORDER BY column %r is not in the DISTINCT list" % (o.expr,))
         if aggs and (plain_cols or star) and not q.group_by:
             # (the reference: "... should appear in GROUP BY clause", CalciteSqlParser.validateGroupByClause)
             raise ValueError("plain columns next to aggregations without GROUP BY: %r" % (plain_cols or "*",))
@@ -570,7 +598,8 @@ def query_columns(query):
             names.append(f.column)
     if query.filter is not None:
         walk(query.filter)
-    for n in list(query.group_by) + [a.column for a in query.aggregations if a.column]:
+    for n in list(query.group_by) + [a.column for a in query.aggregations if a.column] + \
+            (list(query.select_columns) if query.is_distinct else []):
         if n not in names:
             names.append(n)
     return names

@@ -183,6 +183,37 @@ def final_result_table(res: IntermediateResult, query: Q.Query):
     return out
 
 
+def merge_distinct(results, query: Q.Query):
+    """Broker reduce of a distinct query (DistinctDataTableReducer.java:56,122 over DistinctTable.mergeTable): `results`
+    are the servers' DistinctResults (engine.DistinctExecutor). The value records of all servers, each once, under the
+    completed order (distinct.completed_order), cut at the limit alone (the offset is not applied, as in the reference).
+    Returns (column names, rows)."""
+    from . import distinct as D
+    results = list(results)
+    if not results:
+        return list(query.select_columns), []
+    cols, types = list(results[0].columns), list(results[0].column_types)
+    for r in results[1:]:
+        if list(r.columns) != cols:
+            raise ValueError("servers disagree on the distinct columns")
+    seen, records = set(), []
+    for r in results:
+        for row in r.rows:
+            k = tuple(S_key(v, dt) for v, dt in zip(row, types))
+            if k not in seen:
+                seen.add(k)
+                records.append(list(row))
+    rows = D.sort_records(records, types, D.completed_order(query))
+    return cols, rows[:int(query.limit)]
+
+
+def S_key(value, data_type):
+    """A record component as a hashable key that is equal exactly when the reference's values are (Double.compare
+    equality for floating values)."""
+    from . import selection as S
+    return S.row_sort_key(value, data_type)
+
+
 def merge_selection(results, query: Q.Query):
     """Broker reduce of a selection: `results` are the servers' SelectionResults (engine.SelectionExecutor) in server
     order, each sorted by the ORDER BY comparator. Merges them under that comparator (ties: server order, then the

@@ -8,7 +8,11 @@
              ORDER BY clicks DESC LIMIT 10 (selection_topk: the fused filter + top-K scan), and beside it
              SELECT MAX(clicks) with the same WHERE (max_same_where: the same bytes through the lane kernels)
 
-python tools/bench_configs.py [--workload highcard|star|selection|all] [--segments S] [--docs D] [--reps R]
+  distinct : SELECT DISTINCT as the key-presence bitmap scan against GROUP BY COUNT(*) of the same columns and WHERE:
+             (a) configs[1]'s table, DISTINCT daysSinceEpoch under the 10 % filter (LDS bitmap); (b) configs[2]'s table,
+             DISTINCT d1, d2 over every doc (1024 x 1024 keys), as the planner runs it and with distinct_lds = 0
+
+python tools/bench_configs.py [--workload highcard|star|selection|distinct|all] [--segments S] [--docs D] [--reps R]
 Prints one JSON line per (workload, plan): scan-kernel ms per launch (HIP events around back-to-back launches on
 the launch stream), rows/s, forward-index bytes staged per launch and GB/s, fetch ms, groups.
 """
@@ -366,6 +370,111 @@ def run_selection(nseg, docs, reps, warm=0, check=False, tuning=None, cpu_sample
         g.close()
 
 
+def run_distinct(nseg, docs, reps, warm=0, tuning=None):
+    """The distinct workload: per line the scan ms per launch (HIP events around back-to-back reset + scan launches after
+    `warm` untimed ones), the finish (fetch) ms, the strategy, and the algorithmic bytes (the staged bits of the filter
+    and DISTINCT columns, bench.algorithmic_bytes) against 8 TB/s; the yardstick lines are GROUP BY COUNT(*) over the
+    same columns with the same WHERE."""
+    import torch
+    from pinot_amd import parse_sql
+    from pinot_amd import _lib as L
+    from pinot_amd.engine import DistinctExecutor, GpuQueryExecutor, GpuSegment
+    B = _bench()
+    sec = B.secondary_query(B.SECONDARY[0][1])
+    where = sec[sec.index(" WHERE "):sec.index(" GROUP BY")]
+    groups = (
+        (lambda i: B.make_segment(100 + i, docs), (
+            ("a_distinct_days", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where, None),
+            # the scan taken apart (tuning debug_emit, results invalid: pa_scan.h "distinct"): without the in-wave
+            # combining, without the LDS atomics, without both; and the global variant on the same query
+            ("a_distinct_days_no_combine", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where,
+             {"debug_emit": 4}),
+            ("a_distinct_days_no_atomic", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where,
+             {"debug_emit": 1}),
+            ("a_distinct_days_keys_only", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where,
+             {"debug_emit": 5}),
+            ("a_distinct_days_global", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where,
+             {"distinct_lds": 0}),
+            ("a_groupby_count", "SELECT daysSinceEpoch, COUNT(*) FROM AdAnalyticsTable%s GROUP BY daysSinceEpoch "
+                                "TOP 1000" % where, None),
+            # the same yardstick through the generic kernels the distinct scan shares: STRAT_LDS lane-major, step-major
+            ("a_groupby_count_generic", "SELECT daysSinceEpoch, COUNT(*) FROM AdAnalyticsTable%s GROUP BY daysSinceEpoch "
+                                        "TOP 1000" % where, "generic"),
+            ("a_groupby_count_stepmajor", "SELECT daysSinceEpoch, COUNT(*) FROM AdAnalyticsTable%s GROUP BY "
+                                          "daysSinceEpoch TOP 1000" % where, "stepmajor"))),
+        (lambda i: highcard_segment(i, docs), (
+            ("b_distinct_d1_d2", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", None),
+            ("b_distinct_d1_d2_global", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"distinct_lds": 0}),
+            ("b_distinct_d1_d2_lds", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"distinct_lds": 2}),
+            # line (b) taken apart: the tile stream alone (PA_QF_DEBUG_STREAM_ONLY), + filter and keys (no word load, no
+            # atomic), + the word loads (no atomic), the full scan above; and a plain atomic per doc instead of
+            # test-before-set, with and without the in-wave combining
+            ("b_stream_only", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", "stream"),
+            ("b_keys_only", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"debug_emit": 3}),
+            ("b_keys_loads", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"debug_emit": 1}),
+            ("b_plain_atomic", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"debug_emit": 8}),
+            ("b_plain_atomic_no_combine", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"debug_emit": 12}),
+            ("b_no_combine", "SELECT DISTINCT d1, d2 FROM t LIMIT 1000000", {"debug_emit": 4}),
+            ("b_groupby_count", "SELECT d1, d2, COUNT(*) FROM t GROUP BY d1, d2 TOP 1000000", None))),
+    )
+    stream = torch.cuda.current_stream()
+    sp = stream.cuda_stream
+    for make, lines in groups:
+        gsegs, cids = [], None
+        for i in range(nseg):
+            seg = make(i)
+            cids = cids or {n: j for j, n in enumerate(sorted(seg.columns))}
+            gsegs.append(GpuSegment(seg, column_ids=cids, device=0))
+            for c in seg.columns.values():
+                c.fwd_bytes = None
+            log("distinct: segment %d of %d resident" % (i + 1, nseg))
+        for name, sql, tune in lines:
+            q = parse_sql(sql)
+            tn = dict(tuning or {}, **(tune if isinstance(tune, dict) else {}))
+            flags = 0 if not isinstance(tune, str) else L.PA_QF_DEBUG_STREAM_ONLY if tune == "stream" else (
+                L.PA_QF_NO_DENSE_GROUP | L.PA_QF_NO_JIT | (L.PA_QF_NO_LANE_MAJOR if tune == "stepmajor" else 0))
+            invalid = tune == "stream" or "debug_emit" in tn  # (a scan that skips work: timed, never fetched)
+            ex = (DistinctExecutor(q, gsegs, tuning=tn, force_scan=True, flags=flags) if q.is_distinct
+                  else GpuQueryExecutor(q, gsegs, tuning=tn, flags=flags))
+            for _ in range(1 + warm):
+                ex.execute(sp)
+            torch.cuda.synchronize()
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            samples = []
+            for _ in range(reps):
+                ex.reset(sp)
+                a.record(stream)
+                ex.scan(sp)
+                b.record(stream)
+                torch.cuda.synchronize()
+                samples.append(a.elapsed_time(b))
+            ms = float(np.median(samples))
+            out = {"workload": "distinct", "plan_name": name, "kernel_ms": round(ms, 4),
+                   "kernel_ms_min": round(min(samples), 4), "kernel_ms_max": round(max(samples), 4),
+                   "plan": ex.stats()["plan"], "segments": nseg, "docs_per_segment": docs, "warm": warm, "reps": reps}
+            if invalid:
+                out["results_invalid"] = tune if isinstance(tune, str) else tn
+            else:
+                ex.execute(sp)
+                torch.cuda.synchronize()
+                t1 = time.perf_counter()
+                res = ex.fetch(sp, execution_stats=False)
+                fetch_ms = (time.perf_counter() - t1) * 1e3
+                matched = int(L.lib().pa_query_matched_docs(ex.handle))
+                algo = B.algorithmic_bytes(ex, matched)
+                out.update(fetch_ms=round(fetch_ms, 2), matched_docs=matched,
+                           rows=len(res.rows) if q.is_distinct else len(res.groups),
+                           roofline={"bound": "hbm", "achieved": algo / (ms * 1e-3) / 1e9, "peak": 8000.0,
+                                     "unit": "GB/s", "frac": algo / (ms * 1e-3) / 1e9 / 8000.0,
+                                     "algorithmic_bytes_per_launch": algo})
+                if q.is_distinct:
+                    out["present"] = res.present
+            print(json.dumps(out), flush=True)
+            ex.close()
+        for g in gsegs:
+            g.close()
+
+
 def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None, cpu_sample=0, exec_stats=False,
         warm=0, check=False, tuning=None):
     import torch
@@ -523,6 +632,9 @@ def main():
                     for ps in (1, 2, 3) for wg in (0, 1, 2)]
     import torch
     torch.cuda.set_device(0)
+    if args.workload == "distinct":
+        run_distinct(args.segments, args.docs, args.reps, args.warm, tuning)
+        return
     if args.workload == "selection":
         run_selection(args.segments, args.docs, args.reps, args.warm, args.check, tuning, args.cpu_sample)
         return
