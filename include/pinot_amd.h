@@ -78,6 +78,7 @@ extern "C" {
 #define PA_MAX_ORDER_BY 8         /* ORDER BY columns of a selection */
 #define PA_MAX_SELECT_COLUMNS 64  /* output columns of a selection */
 #define PA_MAX_SELECT_ROWS 65536  /* rows a selection keeps (offset + limit) */
+#define PA_MAX_AGG_FILTERS 8      /* distinct aggregation filters (AGG(x) FILTER (WHERE ...)) of one query */
 
 /* error codes */
 #define PA_OK 0
@@ -382,6 +383,49 @@ int pa_query_set_distinct(pa_query* q, const pa_distinct_spec* spec);
  * capacity = 0 only counts. Synchronises `stream`. */
 int64_t pa_query_fetch_distinct(pa_query* q, void* stream, int64_t capacity, int32_t* out_ids, int64_t* out_present);
 
+/* ---------------------------------------------------------------- filtered aggregations
+ * AGG(col) FILTER (WHERE f) (AggregationFunctionUtils.buildFilteredAggregationInfos :312-396,
+ * FilteredAggregationOperator.java:66-101, FilteredGroupByOperator.java:107-200). Aggregations with an equal filter
+ * share a lane; the ones without a filter form the main lane; lane j aggregates the docs matching W AND F_j, where W is
+ * the spec's filter. One fused scan streams the columns once and applies every lane's filter to the docs W kept.
+ *
+ * The filters' leaves are appended to pa_query_spec.leaves after the main filter's (inside PA_MAX_LEAVES), so
+ * pa_query_bind_segment's pa_leaf_params bind them like any other leaf; spec.ops holds only the main filter's program.
+ * spec.aggs may then hold the same (type, column) several times under different filters, and several PA_AGG_COUNT
+ * entries (a filtered COUNT is its lane's doc count: pa_query_fetch_lane_counts; pa_query_fetch writes the group's
+ * count for every PA_AGG_COUNT).
+ *
+ * A group exists when any lane saw a doc of it (the shared group-key generator, FilteredGroupByOperator.java:117-150):
+ * PA_ACC_COUNT_U64 counts the docs of the union of the lanes, which is W when some aggregation has no filter.
+ * Accumulators of a lane that saw no doc of a group stay at their reset identities; the lane count tells (MIN / MAX of
+ * such a cell are not meaningful in pa_query_fetch's output).
+ *
+ * pa_query_prepare fails with PA_EUNSUPPORTED for a hashed key space, for multi-value columns anywhere but a leaf of the
+ * main filter, for PA_AGG_VALUE_HISTOGRAM / PA_AGG_COUNT_MV under a filtered query, and when numGroupsLimit trimming
+ * would run (the reference's first-seen order is lane-major). */
+typedef struct {
+  int32_t num_filters;                        /* 1..PA_MAX_AGG_FILTERS */
+  int32_t num_ops[PA_MAX_AGG_FILTERS];        /* >= 1 */
+  int32_t ops[PA_MAX_AGG_FILTERS][PA_MAX_OPS]; /* postfix programs (PA_OP_*) over pa_query_spec.leaves */
+  int32_t agg_filter[PA_MAX_AGGS];            /* per spec.aggs[i]: its filter, or -1 (the main lane) */
+} pa_agg_filter_spec;
+
+/* Between pa_query_create and the first pa_query_bind_segment. PA_EINVAL: counts out of range, a malformed program, a
+ * filter no aggregation uses; PA_EUNSUPPORTED: a filter expanding to more than PA_MAX_LEAVES CNF literals. */
+int pa_query_set_agg_filters(pa_query* q, const pa_agg_filter_spec* spec);
+
+/* Docs of every lane in the groups the last pa_query_fetch returned, in the same order (num_groups = that call's
+ * result): out[j * num_groups + g] (int64[num_filters * num_groups]) = docs of group g matching W AND F_j. The host
+ * reads COUNT and AVG of a filtered aggregation from it. Synchronises `stream`. */
+int pa_query_fetch_lane_counts(pa_query* q, void* stream, int64_t num_groups, int64_t* out);
+
+/* Per bound segment s of the last scan: out[s * (num_filters + 1)] = docs matching W, out[s * (num_filters + 1) + 1 + j]
+ * = docs matching W AND F_j (int64[num_segments * (num_filters + 1)]): what numDocsScanned and
+ * numEntriesScannedPostFilter of a filtered query are summed from (FilteredAggregationOperator.java:96-98,
+ * FilteredGroupByOperator.java:159-161), with each segment's own lane structure. After a pa_query_fetch of that scan it
+ * returns the counters that fetch read with its own copy (no synchronisation); else it synchronises the device. */
+int pa_query_lane_docs(pa_query* q, int64_t* out);
+
 /* Tests and measurement only: overrides one planner decision of this query (the tunings, their ranges and defaults:
  * pinot_amd/csrc/pa_tuning.h; the library reads none of them from the environment). Before pa_query_prepare.
  * PA_EINVAL: unknown name, value outside the tuning's range, or query already prepared. */
@@ -424,6 +468,8 @@ int pa_query_scan(pa_query* q, void* stream);
                               bin stays 0). 64 bits: a GPU holds tens of billions of docs, so one bin can pass 2^32 */
 #define PA_ACC_KEYBITS_U32 11 /* reduce bitwise OR; distinct queries: bit (key & 31) of word (key >> 5) = the key is
                                  present; the only per-key section of such a query (reset identity 0) */
+#define PA_ACC_LANE_COUNT_U64 12 /* reduce SUM; filtered aggregations: [lane * num_keys + key] = docs of that lane (W AND
+                                    F_lane) in that group (reset identity 0) */
 /* All sections live in one device block of pa_query_accumulator_bytes() bytes (256-byte aligned sections).
  * pa_query_set_accumulator_buffer lets the caller own that block (e.g. memory its collective library
  * registered) instead of the library: call after pa_query_prepare; `bytes` must be >= the size. */

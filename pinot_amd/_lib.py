@@ -15,7 +15,9 @@ PA_MAX_AGGS = 16
 PA_MAX_ORDER_BY = 8
 PA_MAX_SELECT_COLUMNS = 64
 PA_MAX_SELECT_ROWS = 65536
+PA_MAX_AGG_FILTERS = 8
 
+PA_OK, PA_EINVAL, PA_EHIP, PA_ENOMEM, PA_EUNSUPPORTED = 0, -1, -2, -3, -4
 PA_INT, PA_LONG, PA_FLOAT, PA_DOUBLE, PA_STRING, PA_BYTES = range(6)
 PA_LEAF_DICT_RANGE, PA_LEAF_DICT_SET, PA_LEAF_RAW_RANGE, PA_LEAF_MV_DICT_RANGE, PA_LEAF_MV_DICT_SET, PA_LEAF_RAW_SET = range(6)
 PA_OP_LEAF, PA_OP_AND, PA_OP_OR, PA_OP_NOT = range(4)
@@ -53,7 +55,8 @@ PA_STATS_NON_SCAN, PA_STATS_HOST = -1, -2
 PA_BIT_AND, PA_BIT_OR, PA_BIT_NOT = -1, -2, -3
 PA_BIT_PROG_MAX = 64
 PA_ACC_COUNT_U64, PA_ACC_SUM_I64, PA_ACC_SUM_F64, PA_ACC_MIN_I64, PA_ACC_MAX_I64, PA_ACC_HLL_U8, \
-    PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64, PA_ACC_KEYBITS_U32 = range(12)
+    PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64, PA_ACC_KEYBITS_U32, \
+    PA_ACC_LANE_COUNT_U64 = range(13)
 PA_MAX_PERCENTILES = 64
 ABI_VERSION = 5
 
@@ -67,6 +70,7 @@ EXPORTED = [
     "pa_query_set_selection", "pa_query_bind_order_remap", "pa_query_fetch_selection",
     "pa_query_selection_segment_docs", "pa_query_selection_counters",
     "pa_query_set_distinct", "pa_query_fetch_distinct",
+    "pa_query_set_agg_filters", "pa_query_fetch_lane_counts", "pa_query_lane_docs",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
     "pa_query_partition_keys",
@@ -136,6 +140,15 @@ class DistinctSpec(ctypes.Structure):
     ]
 
 
+class AggFilterSpec(ctypes.Structure):
+    _fields_ = [
+        ("num_filters", ctypes.c_int32),
+        ("num_ops", ctypes.c_int32 * PA_MAX_AGG_FILTERS),
+        ("ops", (ctypes.c_int32 * PA_MAX_OPS) * PA_MAX_AGG_FILTERS),
+        ("agg_filter", ctypes.c_int32 * PA_MAX_AGGS),
+    ]
+
+
 class LeafParams(ctypes.Structure):
     _fields_ = [
         ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("negate", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -177,6 +190,9 @@ def _declare(lib):
         "pa_query_selection_counters": (ctypes.c_int, [vp, vp]),
         "pa_query_set_distinct": (ctypes.c_int, [vp, ctypes.POINTER(DistinctSpec)]),
         "pa_query_fetch_distinct": (i64, [vp, vp, i64, vp, ctypes.POINTER(i64)]),
+        "pa_query_set_agg_filters": (ctypes.c_int, [vp, ctypes.POINTER(AggFilterSpec)]),
+        "pa_query_fetch_lane_counts": (ctypes.c_int, [vp, vp, i64, vp]),
+        "pa_query_lane_docs": (ctypes.c_int, [vp, vp]),
         "pa_query_prepare": (ctypes.c_int, [vp]),
         "pa_query_num_keys": (i64, [vp]),
         "pa_query_execute": (ctypes.c_int, [vp, vp]),
@@ -238,7 +254,9 @@ def lib():
 
 def check(rc, what=""):
     if rc < 0:
-        raise PinotAmdError("%s failed (%d): %s" % (what, rc, lib().pa_last_error().decode(errors="replace")))
+        err = PinotAmdError("%s failed (%d): %s" % (what, rc, lib().pa_last_error().decode(errors="replace")))
+        err.code = rc  # PA_E*
+        raise err
     return rc
 
 

@@ -42,6 +42,59 @@ int pa_query_set_tuning(pa_query* q, const char* name, int32_t value) {
 
 int32_t pa_query_results_invalid(const pa_query* q) { return q ? (tuning_invalidating(q->tune) ? 1 : 0) : -1; }
 
+int pa_query_set_agg_filters(pa_query* q, const pa_agg_filter_spec* spec) {
+  if (!q || !spec) return fail(PA_EINVAL, "null query or aggregation-filter spec");
+  if (q->prepared) return fail(PA_EINVAL, "query already prepared");
+  for (const pa_segment* seg : q->segs)
+    if (seg) return fail(PA_EINVAL, "set the aggregation filters before binding segments");
+  if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "aggregation filters on a selection or distinct query");
+  const pa_query_spec& s = q->spec;
+  if (spec->num_filters < 1 || spec->num_filters > PA_MAX_AGG_FILTERS)
+    return fail(PA_EINVAL, "aggregation filters: 1.." + std::to_string(PA_MAX_AGG_FILTERS) + " filters");
+  std::vector<char> used(spec->num_filters, 0);
+  for (int a = 0; a < s.num_aggs; ++a) {
+    const int f = spec->agg_filter[a];
+    if (f < -1 || f >= spec->num_filters) return fail(PA_EINVAL, "aggregation filter index out of range");
+    if (f >= 0) used[f] = 1;
+  }
+  std::vector<std::vector<Literal>> lits(spec->num_filters);
+  std::vector<std::vector<int>> ends(spec->num_filters);
+  size_t total = 0;
+  for (int f = 0; f < spec->num_filters; ++f) {
+    if (!used[f]) return fail(PA_EINVAL, "an aggregation filter no aggregation uses");
+    if (spec->num_ops[f] < 1 || spec->num_ops[f] > PA_MAX_OPS) return fail(PA_EINVAL, "aggregation filter: bad program length");
+    std::vector<Clause> cnf;
+    if (int rc = to_cnf_program(spec->ops[f], spec->num_ops[f], s.num_leaves, cnf)) return rc;
+    for (const Clause& c : cnf)
+      for (size_t i = 0; i < c.size(); ++i) {
+        lits[f].push_back(c[i]);
+        ends[f].push_back(i + 1 == c.size());
+      }
+    total += lits[f].size();
+  }
+  if (total > PA_MAX_LEAVES)
+    return fail(PA_EUNSUPPORTED, "aggregation filters expand to more than PA_MAX_LEAVES CNF literals");
+  q->filt_spec = *spec;
+  q->filt_lits = lits;
+  q->filt_clause_end = ends;
+  q->is_filtered = true;
+  return PA_OK;
+}
+
+int pa_query_lane_docs(pa_query* q, int64_t* out) {
+  if (!q || !q->prepared || !out) return fail(PA_EINVAL, "query not prepared");
+  if (!q->is_filtered) return fail(PA_EINVAL, "not a query with aggregation filters");
+  const size_t n = (size_t)q->nseg * (q->filt_spec.num_filters + 1);
+  if (!q->scanned_since_fetch && q->last_matched >= 0 && q->filt_seg_docs_host.size() == n) {
+    // the last pa_query_fetch read the counters with its own copy, after the last scan: no second synchronisation
+    std::copy(q->filt_seg_docs_host.begin(), q->filt_seg_docs_host.end(), out);
+    return PA_OK;
+  }
+  PA_HIP(hipDeviceSynchronize());
+  PA_HIP(hipMemcpy(out, q->filt_seg_docs.p, n * 8, hipMemcpyDeviceToHost));
+  return PA_OK;
+}
+
 int pa_query_bind_segment(pa_query* q, int32_t index, const pa_segment* seg, const pa_leaf_params* leaf_params,
                           const int32_t* const* group_remaps) {
   if (!q || !seg || index < 0 || index >= q->nseg) return fail(PA_EINVAL, "bad bind arguments");
@@ -120,8 +173,10 @@ int pa_query_prepare(pa_query* q) {
   if (!rc) rc = plan_slots(q, P);
   if (!rc) rc = plan_key_space(q, P);
   if (!rc) rc = plan_limit(q, P);
-  if (!rc && !q->is_distinct) rc = plan_gdense(q, P);  // (a distinct query has its own two strategies)
+  // (a distinct query and a query with aggregation filters have their own two strategies each)
+  if (!rc && !q->is_distinct && !q->is_filtered) rc = plan_gdense(q, P);
   if (!rc) rc = build_segments(q, P);
+  if (!rc && q->is_filtered) rc = filtered_validate(q, P);
   if (!rc) rc = plan_walk(q, P);
   if (!rc) rc = plan_accumulators(q, P);
   TilePlan plan, count_plan;
@@ -144,6 +199,10 @@ int pa_query_prepare(pa_query* q) {
   q->plan_ring = plan.ring;
   q->plan_wg = plan.wg_per_cu;
   fill_devquery(q, P, plan, total_tiles);
+  if (q->is_filtered) {
+    rc = filtered_plan(q, P);
+    if (rc) return rc;
+  }
   rc = plan_leaps(q, P);
   if (rc) return rc;
 
@@ -233,6 +292,8 @@ int pa_query_reset(pa_query* q, void* stream) {
   char* block = (char*)(q->external_acc ? q->external_acc : q->acc.p);
   if (q->is_select)
     if (int rc = select_reset(q, st)) return rc;
+  // (the lane counts lie in the block: identity 0, like every SUM section; the per-segment doc counters do not)
+  if (q->is_filtered) PA_HIP(hipMemsetAsync(q->filt_seg_docs.p, 0, q->filt_seg_docs.n, st));
   // Small blocks (the common case): one launch writes zeros and identities (the block is whole 256-byte units). Larger
   // ones keep the memsets, whose rate matters there and whose extra launches no longer do.
   auto identity = [](const Section& sc, int64_t& v) {
@@ -402,6 +463,10 @@ int pa_query_set_accumulator_buffer(pa_query* q, void* device_buffer, uint64_t b
     }
   };
   relocate(q->hq);
+  if (q->is_filtered) {
+    q->hfilt.lane_count = (unsigned long long*)q->sections[q->lane_section].ptr;
+    PA_HIP(hipMemcpy(q->filt_desc.p, &q->hfilt, sizeof(FiltDesc), hipMemcpyHostToDevice));
+  }
   if (q->limit_mode) q->limit.reached = q->hq.matched_docs + 2;
   PA_HIP(hipMemcpy(q->dq.p, &q->hq, sizeof(DevQuery), hipMemcpyHostToDevice));
   if (q->jit_fn) {

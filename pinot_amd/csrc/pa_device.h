@@ -59,9 +59,16 @@ enum Strategy : int32_t {
   STRAT_SELECT = 128,
   // distinct (SELECT DISTINCT ...): filter + one bit per key of the direct key space (pa_scan.h "distinct"): the
   // workgroup-private LDS bitmap, flushed once per workgroup, or test-before-set on the bitmap in HBM
-  STRAT_DISTINCT_LDS = 129, STRAT_DISTINCT = 130
+  STRAT_DISTINCT_LDS = 129, STRAT_DISTINCT = 130,
+  // filtered aggregations (AGG(x) FILTER (WHERE ...)): filter + one mask per aggregation filter ("lane") over the
+  // surviving docs + per-lane aggregation (pa_scan.h "filtered aggregations"): workgroup-private accumulators in LDS,
+  // flushed once per workgroup, or device-scope atomics
+  STRAT_FILTERED_LDS = 131, STRAT_FILTERED = 132
 };
 __host__ __device__ constexpr bool is_distinct(int s) { return s == STRAT_DISTINCT_LDS || s == STRAT_DISTINCT; }
+__host__ __device__ constexpr bool is_filtered(int s) { return s == STRAT_FILTERED_LDS || s == STRAT_FILTERED; }
+// strategies whose accumulators (Acc<STRAT>) are the workgroup's LDS copies
+__host__ __device__ constexpr bool acc_in_lds(int s) { return s == STRAT_LDS || s == STRAT_FILTERED_LDS; }
 __host__ __device__ constexpr bool is_pcount(int s) { return s == STRAT_PCOUNT || s == STRAT_PCOUNT_MV; }
 // STRAT_GDENSE: 4-wave workgroups; STRAT_GDENSE8 / STRAT_GDENSE12: the same kernel with 8- / 12-wave workgroups (2 / 3
 // waves per SIMD when one workgroup fits a CU, e.g. beside a 64 KiB value table: the walk's LDS round trips and VALU
@@ -331,6 +338,25 @@ struct DevQuery {
   int64_t leap_slices;           // scan waves (grid x waves per workgroup): one list slice each
   const struct SelDesc* sel;     // STRAT_SELECT: the selection's descriptor (nullptr otherwise)
   uint32_t* keybits;             // distinct: the key-presence bitmap (PA_ACC_KEYBITS_U32), (num_keys + 31) / 32 words
+  const struct FiltDesc* filt;   // filtered aggregations: the lanes' descriptor (nullptr otherwise)
+};
+// ---------------------------------------------------------------- filtered aggregations (STRAT_FILTERED_LDS / STRAT_FILTERED)
+// AGG(x) FILTER (WHERE F): aggregations with an equal filter share a lane (AggregationFunctionUtils.java:340-373), the
+// ones without a filter form the main lane. Lane j aggregates the docs matching W AND F_j (W: the query's filter, the
+// scan's survivors). Lane index num_lanes stands for the main lane in lane_naggs / lane_aggs.
+struct FiltDesc {
+  int32_t num_lanes;               // aggregation filters (1..PA_MAX_AGG_FILTERS)
+  int32_t has_main;                // some aggregation has no filter: the union of the lanes is W
+  int32_t num_lits;                // CNF literals of all lanes together
+  int32_t pad;
+  int32_t lit_begin[PA_MAX_AGG_FILTERS + 1];  // lane j's literals (clause-major): [lit_begin[j], lit_begin[j + 1])
+  int32_t lane_naggs[PA_MAX_AGG_FILTERS + 1];
+  int32_t lane_aggs[PA_MAX_AGG_FILTERS + 1][PA_MAX_AGGS];  // the lane's aggregations (indices into DevQuery::aggs)
+  const DevLeaf* leaves;           // [num_segments][num_lits]: the literals for every segment
+  unsigned long long* lane_count;  // PA_ACC_LANE_COUNT_U64: [lane * num_keys + key] docs of the lane in the group
+  unsigned long long* seg_docs;    // [num_segments][num_lanes + 1]: docs matching W, then W AND F_j (own buffer)
+  uint32_t lds_lane_count_off;     // STRAT_FILTERED_LDS: byte offset of the workgroup's u32 [lane * num_keys + key]
+  uint32_t pad1;
 };
 // ---------------------------------------------------------------- selection (STRAT_SELECT)
 // One candidate of the top-K: (key, row) compared as one 128-bit unsigned number. key = the ORDER BY components,

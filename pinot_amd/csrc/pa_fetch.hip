@@ -8,7 +8,60 @@ static int refuse_invalid(const pa_query* q) {
   return t ? fail(PA_EINVAL, std::string("results invalid: tuning ") + t + " is set") : PA_OK;
 }
 
+// Filtered aggregations: out[j * n + g] = lane j's docs in fetched group g (PA_ACC_LANE_COUNT_U64 at keys[g]).
+__global__ void __launch_bounds__(256) lane_count_gather_kernel(const unsigned long long* __restrict__ lane_count,
+                                                                 int64_t num_keys, const int64_t* __restrict__ keys,
+                                                                 int64_t n, int lanes, int64_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n * lanes) return;
+  const int64_t j = i / n, g = i - j * n;
+  out[i] = (int64_t)lane_count[j * num_keys + keys[g]];
+}
+
 extern "C" {
+int pa_query_fetch_lane_counts(pa_query* q, void* stream, int64_t num_groups, int64_t* out) {
+  if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
+  if (!q->is_filtered) return fail(PA_EINVAL, "not a query with aggregation filters");
+  if (int rc = refuse_invalid(q)) return rc;
+  if (num_groups < 0 || num_groups > INT32_MAX || (num_groups > 0 && !out)) return fail(PA_EINVAL, "fetch lane counts: bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  // the keys pa_query_fetch returns for the current accumulators: the same compaction passes as the fetch
+  const int64_t K = q->num_keys;
+  const int64_t nb = (K + 2047) / 2048;
+  if ((int64_t)q->fetch_blocks.n < (nb + 1) * 4) {
+    dev_free(q->fetch_blocks);
+    if (int rc = dev_alloc(q->fetch_blocks, (size_t)(nb + 1) * 4)) return rc;
+  }
+  const int all = q->spec.num_group_by != 0 ? 0 : 1;
+  const unsigned long long* count = (const unsigned long long*)q->sections[0].ptr;
+  uint32_t total = 0;
+  PA_HIP(launch_compact(count, K, all, (uint32_t*)q->fetch_blocks.p, 0, nullptr, 0, st));
+  PA_HIP(hipMemcpyAsync(&total, (uint32_t*)q->fetch_blocks.p + nb, 4, hipMemcpyDeviceToHost, st));
+  PA_HIP(hipStreamSynchronize(st));
+  if ((int64_t)total != num_groups)
+    return fail(PA_EINVAL, "num_groups is not the group count pa_query_fetch returns for these accumulators");
+  if (num_groups == 0) return PA_OK;
+  const int lanes = q->filt_spec.num_filters;
+  const size_t out_at = ((size_t)num_groups * 8 + 255) & ~(size_t)255;
+  const size_t bytes = out_at + (size_t)num_groups * lanes * 8;
+  if (q->lane_buf.n < bytes || !q->lane_buf.p) {
+    dev_free(q->lane_buf);
+    if (int rc = dev_alloc(q->lane_buf, bytes)) return rc;
+  }
+  CompactDesc d;
+  std::memset(&d, 0, sizeof(d));
+  d.keys = (int64_t*)q->lane_buf.p;
+  PA_HIP(launch_compact(count, K, all, (uint32_t*)q->fetch_blocks.p, num_groups, &d, 1, st));
+  int64_t* dout = (int64_t*)((char*)q->lane_buf.p + out_at);
+  const int64_t cells = num_groups * lanes;
+  lane_count_gather_kernel<<<(unsigned)((cells + 255) / 256), 256, 0, st>>>(
+      (const unsigned long long*)q->sections[q->lane_section].ptr, K, d.keys, num_groups, lanes, dout);
+  PA_HIP(hipGetLastError());
+  PA_HIP(hipMemcpyAsync(out, dout, (size_t)cells * 8, hipMemcpyDeviceToHost, st));
+  PA_HIP(hipStreamSynchronize(st));
+  return PA_OK;
+}
+
 int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out_keys, int64_t* out_counts,
                        void* const* out_aggs) {
   if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
@@ -82,6 +135,9 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
       }
     }
     PA_HIP(hipMemcpyAsync(q->host_acc, dbase, q->acc.n, hipMemcpyDeviceToHost, st));
+    if (q->is_filtered && !q->filt_seg_docs_host.empty())  // (the lanes' per-segment docs ride on this synchronisation: pa_query_lane_docs)
+      PA_HIP(hipMemcpyAsync(q->filt_seg_docs_host.data(), q->filt_seg_docs.p, q->filt_seg_docs_host.size() * 8,
+                            hipMemcpyDeviceToHost, st));
     PA_HIP(hipStreamSynchronize(st));
     const char* hb = (const char*)q->host_acc;
     auto hsec = [&](int sec) { return hb + ((char*)q->sections[sec].ptr - dbase); };
@@ -121,6 +177,9 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
                         nullptr, 0, st));
   PA_HIP(hipMemcpyAsync(&total, (uint32_t*)q->fetch_blocks.p + nb, 4, hipMemcpyDeviceToHost, st));
   PA_HIP(hipMemcpyAsync(md, q->sections.back().ptr, 32, hipMemcpyDeviceToHost, st));
+  if (q->is_filtered && !q->filt_seg_docs_host.empty())
+    PA_HIP(hipMemcpyAsync(q->filt_seg_docs_host.data(), q->filt_seg_docs.p, q->filt_seg_docs_host.size() * 8,
+                          hipMemcpyDeviceToHost, st));
   PA_HIP(hipStreamSynchronize(st));
   q->last_matched = (int64_t)md[0];
   q->last_reached = (int64_t)md[2];

@@ -333,8 +333,25 @@ struct pa_query {
   DstOrder dst_order{};
   bool dst_key_order = false;
   DevBuf dst_counts, dst_bits2, dst_rows;
+  // filtered aggregations (pa_query_set_agg_filters; pa_scan.h "filtered aggregations"): the spec, every filter's CNF
+  // (literals clause-major over the spec's leaves, with their clause ends), the descriptor the scan reads with its
+  // device copy, every segment's DevLeafs of the lanes' literals, the per-(segment, lane) doc counters and the
+  // fetched groups' keys + lane counts (grown on demand); the PA_ACC_LANE_COUNT_U64 section's index
+  bool is_filtered = false;
+  pa_agg_filter_spec filt_spec{};
+  std::vector<std::vector<Literal>> filt_lits;
+  std::vector<std::vector<int>> filt_clause_end;
+  FiltDesc hfilt{};
+  std::vector<DevLeaf> hfilt_leaves;
+  DevBuf filt_desc, filt_leaves, filt_seg_docs, lane_buf;
+  int lane_section = -1;
+  std::vector<int64_t> filt_seg_docs_host;  // filt_seg_docs as the last fetch read it ([nseg][num_filters + 1])
 
   ~pa_query() {
+    dev_free(filt_desc);
+    dev_free(filt_leaves);
+    dev_free(filt_seg_docs);
+    dev_free(lane_buf);
     dev_free(dst_counts);
     dev_free(dst_bits2);
     dev_free(dst_rows);
@@ -401,6 +418,8 @@ struct Prep {
   bool lm = false;
   size_t lds_acc = 0;  // LDS strategy: accumulator bytes
   std::vector<size_t> agg_lds;
+  size_t lane_count_lds = 0;  // filtered aggregations, LDS variant: byte offset of the workgroup's lane counts
+  bool filt_dense = true;     // filtered aggregations: the lanes' union is expected to keep a doc per wave tile or more
   // STRAT_GDENSE (plan_gdense)
   bool gdense = false;
   std::vector<char> gd_stage_raw;          // per slot: raw aggregation column staged as a 32/64-bit "bit column"
@@ -436,6 +455,9 @@ struct TilePlan {
 // ---------------------------------------------------------------- cross-unit entry points
 // pa_plan.hip
 int upload_owned(pa_query* q, const void* host, size_t bytes, void** dev);
+int to_cnf_program(const int32_t* ops, int num_ops, int num_leaves, std::vector<Clause>& out);
+int filtered_validate(pa_query* q, Prep& P);        // prepare, after build_segments: what a filtered query refuses
+int filtered_plan(pa_query* q, const Prep& P);      // prepare, after fill_devquery: the lanes' descriptor, uploaded
 int mv_group_component(const pa_query* q);
 int plan_filter(pa_query* q, Prep& P);
 int plan_slots(pa_query* q, Prep& P);

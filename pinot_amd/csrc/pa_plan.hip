@@ -9,16 +9,16 @@ struct Node {
 };
 
 // Postfix program -> CNF (list of clauses, each a disjunction of possibly negated leaves).
-int to_cnf(const pa_query_spec& spec, std::vector<Clause>& out) {
+int to_cnf_program(const int32_t* ops, int num_ops, int num_leaves, std::vector<Clause>& out) {
   out.clear();
-  if (spec.num_ops == 0) return PA_OK;
+  if (num_ops == 0) return PA_OK;
   std::vector<Node> nodes;
   std::vector<int> st;
-  for (int i = 0; i < spec.num_ops; ++i) {
-    const int op = spec.ops[i] & 0xff;
+  for (int i = 0; i < num_ops; ++i) {
+    const int op = ops[i] & 0xff;
     if (op == PA_OP_LEAF) {
-      const int leaf = (spec.ops[i] >> 8) & 0xff;
-      if (leaf >= spec.num_leaves) return fail(PA_EINVAL, "filter program references a missing leaf");
+      const int leaf = (ops[i] >> 8) & 0xff;
+      if (leaf >= num_leaves) return fail(PA_EINVAL, "filter program references a missing leaf");
       nodes.push_back({PA_OP_LEAF, leaf});
       st.push_back((int)nodes.size() - 1);
     } else if (op == PA_OP_NOT) {
@@ -74,6 +74,10 @@ int to_cnf(const pa_query_spec& spec, std::vector<Clause>& out) {
     return PA_OK;
   };
   return rec(st.back(), false, out);
+}
+
+int to_cnf(const pa_query_spec& spec, std::vector<Clause>& out) {
+  return to_cnf_program(spec.ops, spec.num_ops, spec.num_leaves, out);
 }
 
 
@@ -220,6 +224,9 @@ int plan_slots(pa_query* q, Prep& P) {
   for (int j = 0; j < s.num_group_by; ++j) P.slot_post[P.gb_slot[j]] = 1;
   for (int a = 0; a < s.num_aggs; ++a)
     if (s.aggs[a].type != PA_AGG_COUNT) P.slot_post[P.agg_slot[a]] = 1;
+  // (the aggregation filters run on the docs the query's own filter kept: their columns are post-filter columns)
+  for (const std::vector<Literal>& lits : q->filt_lits)
+    for (const Literal& lit : lits) P.slot_post[P.leaf_slot[lit.leaf]] = 1;
   int post_bits = 0;
   for (int sl = 0; sl < kMaxSlots; ++sl) {
     if (!P.slot_post[sl] || sl >= (int)q->slot_cols.size() || !q->nseg) continue;
@@ -800,15 +807,13 @@ int build_segments(pa_query* q, Prep& P) {
     }
     if (P.gdense)
       for (int a = 0; a < s.num_aggs; ++a) d.gd_src[a] = P.gd_src[si][a];
-    // filter literals
-    for (size_t li = 0; li < q->literals.size(); ++li) {
-      const Literal lit = q->literals[li];
+    // filter literals (the query's own, then every lane's of a filtered-aggregation query)
+    auto make_leaf = [&](const Literal lit, int clause_end, DevLeaf& L) -> int {
       const pa_leaf_params& p = q->leaf_params[si][lit.leaf];
-      DevLeaf& L = d.leaves[li];
       L.kind = s.leaves[lit.leaf].kind;
       L.slot = P.leaf_slot[lit.leaf];
       L.negate = (p.negate != 0) != lit.neg;
-      L.clause_end = q->clause_end[li];
+      L.clause_end = clause_end;
       const DevCol& dc = d.cols[L.slot];
       L.nbits = dc.nbits;
       L.lds_off = dc.lds_off;
@@ -870,6 +875,22 @@ int build_segments(pa_query* q, Prep& P) {
         L.dlo = p.dlo;
         L.dhi = p.dhi;
       }
+      return PA_OK;
+    };
+    for (size_t li = 0; li < q->literals.size(); ++li) {
+      rc = make_leaf(q->literals[li], q->clause_end[li], d.leaves[li]);
+      if (rc) return rc;
+    }
+    if (q->is_filtered) {
+      if (si == 0) q->hfilt_leaves.clear();
+      for (size_t f = 0; f < q->filt_lits.size(); ++f)
+        for (size_t li = 0; li < q->filt_lits[f].size(); ++li) {
+          DevLeaf L;
+          std::memset(&L, 0, sizeof(L));
+          rc = make_leaf(q->filt_lits[f][li], q->filt_clause_end[f][li], L);
+          if (rc) return rc;
+          q->hfilt_leaves.push_back(L);
+        }
     }
     // group-by remaps
     for (int j = 0; j < s.num_group_by; ++j) {
@@ -1008,6 +1029,11 @@ int plan_accumulators(pa_query* q, Prep& P) {
     sec.push_back({PA_ACC_KEYS_I64, K * (q->key_words == 2 ? 3 : 1)});
     q->keys_section = (int)sec.size() - 1;
   }
+  q->lane_section = -1;
+  if (q->is_filtered) {  // docs of every lane in every group
+    sec.push_back({PA_ACC_LANE_COUNT_U64, (int64_t)q->filt_spec.num_filters * K});
+    q->lane_section = (int)sec.size() - 1;
+  }
   sec.push_back({PA_ACC_DOCS_U64, 4});  // [0] numDocsScanned, [1] group-table overflows, [2] limit reached, [3] errors
   size_t total = 0;
   std::vector<size_t> offs;
@@ -1033,6 +1059,104 @@ int plan_accumulators(pa_query* q, Prep& P) {
                          : (size_t)K * 8 * ((A.type == PA_AGG_SUM && P.agg_src[a] == SRC_LONG) ? 2 : 1);
     P.lds_acc += (bytes + 15) & ~(size_t)15;
   }
+  if (q->is_filtered) {  // (then the workgroup's u32 lane counts)
+    P.lane_count_lds = P.lds_acc;
+    P.lds_acc += ((size_t)q->filt_spec.num_filters * (size_t)K * 4 + 15) & ~(size_t)15;
+  }
+  return PA_OK;
+}
+
+// A filtered-aggregation query against what the scan's lane code covers (pa_scan.h "filtered aggregations").
+int filtered_validate(pa_query* q, Prep& P) {
+  const pa_query_spec& s = q->spec;
+  if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "aggregation filters on a selection or distinct query");
+  if (q->hashed)
+    return fail(PA_EUNSUPPORTED, "filtered aggregations over a hashed key space (a raw group-by column, or a product of "
+                                 "group-by cardinalities too large to address directly) are not supported");
+  if (q->limit_mode || q->limit_walk)
+    return fail(PA_EUNSUPPORTED, "filtered aggregations where numGroupsLimit trimming would run are not supported (the "
+                                 "reference's first-seen order is lane-major)");
+  if (q->has_mv || P.gb_mv)
+    return fail(PA_EUNSUPPORTED, "filtered aggregations over a multi-value group-by or aggregation column are not "
+                                 "supported");
+  for (const std::vector<Literal>& lits : q->filt_lits)
+    for (const Literal& lit : lits) {
+      const int k = s.leaves[lit.leaf].kind;
+      if (k == PA_LEAF_MV_DICT_RANGE || k == PA_LEAF_MV_DICT_SET)
+        return fail(PA_EUNSUPPORTED, "a multi-value column in an aggregation filter is not supported");
+    }
+  for (int a = 0; a < s.num_aggs; ++a) {
+    if (s.aggs[a].type == PA_AGG_VALUE_HISTOGRAM)
+      return fail(PA_EUNSUPPORTED, "VALUE_HISTOGRAM (PERCENTILE) in a query with aggregation filters is not supported");
+    if (s.aggs[a].type == PA_AGG_COUNT_MV)
+      return fail(PA_EUNSUPPORTED, "COUNT_MV in a query with aggregation filters is not supported");
+  }
+  // Density of the lanes' union, for the LDS decision (plan_filter's estimate: matching-dictId fractions, the worst
+  // segment; only speed depends on it): W's when some aggregation has no filter, else W's times the lanes' fractions
+  // added up.
+  bool has_main = false;
+  for (int a = 0; a < s.num_aggs; ++a) has_main |= q->filt_spec.agg_filter[a] < 0;
+  double frac = has_main ? 1.0 : 0.0;
+  for (size_t f = 0; f < q->filt_lits.size() && !has_main; ++f) {
+    double lane = 1.0, clause = 0.0;
+    for (size_t li = 0; li < q->filt_lits[f].size(); ++li) {
+      double worst = 0.0;
+      for (int si = 0; si < q->nseg; ++si)
+        worst = std::max(worst, leaf_selectivity(q, si, q->filt_lits[f][li].leaf, q->filt_lits[f][li].neg));
+      clause += worst;
+      if (q->filt_clause_end[f][li]) {
+        lane *= std::min(1.0, clause);
+        clause = 0.0;
+      }
+    }
+    frac += lane;
+  }
+  const double density = (P.has_filter ? P.post_density : (double)kWTileDocs) * std::min(1.0, frac);
+  P.filt_dense = density >= 1.0;
+  return PA_OK;
+}
+
+// The lanes' descriptor: every lane's literal range and aggregations, the literals of every segment with their staged
+// regions (known once apply_layout ran), the lane-count section and the per-(segment, lane) doc counters.
+int filtered_plan(pa_query* q, const Prep& P) {
+  const pa_query_spec& s = q->spec;
+  const pa_agg_filter_spec& fs = q->filt_spec;
+  FiltDesc& F = q->hfilt;
+  std::memset(&F, 0, sizeof(F));
+  F.num_lanes = fs.num_filters;
+  int nl = 0;
+  for (int f = 0; f < fs.num_filters; ++f) {
+    F.lit_begin[f] = nl;
+    nl += (int)q->filt_lits[f].size();
+  }
+  F.lit_begin[fs.num_filters] = nl;
+  F.num_lits = nl;
+  for (int a = 0; a < s.num_aggs; ++a) {
+    const int lane = fs.agg_filter[a] < 0 ? fs.num_filters : fs.agg_filter[a];
+    if (fs.agg_filter[a] < 0) F.has_main = 1;
+    if (s.aggs[a].type != PA_AGG_COUNT) F.lane_aggs[lane][F.lane_naggs[lane]++] = a;  // (COUNT: the lane's doc count)
+  }
+  if ((int64_t)q->hfilt_leaves.size() != (int64_t)q->nseg * nl) return fail(PA_EINVAL, "internal: lane literals");
+  for (int si = 0; si < q->nseg; ++si)
+    for (int li = 0; li < nl; ++li) {
+      DevLeaf& L = q->hfilt_leaves[(size_t)si * nl + li];
+      L.lds_off = q->hsegs[si].cols[L.slot].lds_off;
+    }
+  int rc = dev_alloc(q->filt_leaves, std::max<size_t>(16, q->hfilt_leaves.size() * sizeof(DevLeaf)));
+  if (!rc) rc = dev_alloc(q->filt_seg_docs, (size_t)std::max(1, q->nseg) * (fs.num_filters + 1) * 8);
+  if (!rc) rc = dev_alloc(q->filt_desc, sizeof(FiltDesc));
+  if (rc) return rc;
+  if (!q->hfilt_leaves.empty())
+    PA_HIP(hipMemcpy(q->filt_leaves.p, q->hfilt_leaves.data(), q->hfilt_leaves.size() * sizeof(DevLeaf),
+                     hipMemcpyHostToDevice));
+  PA_HIP(hipMemset(q->filt_seg_docs.p, 0, q->filt_seg_docs.n));
+  q->filt_seg_docs_host.assign((size_t)q->nseg * (fs.num_filters + 1), 0);
+  F.leaves = (const DevLeaf*)q->filt_leaves.p;
+  F.lane_count = (unsigned long long*)q->sections[q->lane_section].ptr;
+  F.seg_docs = (unsigned long long*)q->filt_seg_docs.p;
+  F.lds_lane_count_off = (uint32_t)P.lane_count_lds;
+  PA_HIP(hipMemcpy(q->filt_desc.p, &F, sizeof(F), hipMemcpyHostToDevice));
+  q->hq.filt = (const FiltDesc*)q->filt_desc.p;
   return PA_OK;
 }
 

@@ -288,39 +288,44 @@ struct Acc {
   const PartScratch* ps;  // partitioned passes only
 
   __device__ __forceinline__ void add_count(int64_t key, uint32_t n) const {
-    if (STRAT == STRAT_LDS) atomicAdd((uint32_t*)(lds + q->lds_count_off) + key, n);
+    if (acc_in_lds(STRAT)) atomicAdd((uint32_t*)(lds + q->lds_count_off) + key, n);
     else __hip_atomic_fetch_add(gp(q->count) + key, (unsigned long long)n, RLX);
   }
   __device__ __forceinline__ void add_i64(const DevAgg& A, int64_t key, int64_t v) const {
-    if (STRAT == STRAT_LDS) atomicAdd((unsigned long long*)(lds + A.lds_off) + key, (unsigned long long)v);
+    if (acc_in_lds(STRAT)) atomicAdd((unsigned long long*)(lds + A.lds_off) + key, (unsigned long long)v);
     else __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + key, (unsigned long long)v, RLX);
   }
   __device__ __forceinline__ void add_f64(const DevAgg& A, int64_t key, double v) const {
-    if (STRAT == STRAT_LDS) atomicAdd((double*)(lds + A.lds_off) + key, v);
+    if (acc_in_lds(STRAT)) atomicAdd((double*)(lds + A.lds_off) + key, v);
     else __hip_atomic_fetch_add(gp(A.acc_f64) + key, v, RLX);
   }
   __device__ __forceinline__ void min_i64(const DevAgg& A, int64_t key, int64_t v) const {
-    if (STRAT == STRAT_LDS) atomicMin((long long*)(lds + A.lds_off) + key, (long long)v);
+    if (acc_in_lds(STRAT)) atomicMin((long long*)(lds + A.lds_off) + key, (long long)v);
     else __hip_atomic_fetch_min(gp((long long*)A.acc_i64) + key, (long long)v, RLX);
   }
   __device__ __forceinline__ void max_i64(const DevAgg& A, int64_t key, int64_t v) const {
-    if (STRAT == STRAT_LDS) atomicMax((long long*)(lds + A.lds_off) + key, (long long)v);
+    if (acc_in_lds(STRAT)) atomicMax((long long*)(lds + A.lds_off) + key, (long long)v);
     else __hip_atomic_fetch_max(gp((long long*)A.acc_i64) + key, (long long)v, RLX);
   }
   // DISTINCTCOUNT: the group saw value id v (an idempotent byte store: no atomic needed)
   __device__ __forceinline__ void set_presence(const DevAgg& A, int64_t key, int64_t v) const {
-    if (STRAT == STRAT_LDS) ((uint8_t*)(lds + A.lds_off))[key * A.nvals + v] = 1;
+    if (acc_in_lds(STRAT)) ((uint8_t*)(lds + A.lds_off))[key * A.nvals + v] = 1;
     else gp(A.acc_hll)[key * A.nvals + v] = 1;
   }
   // VALUE_HISTOGRAM: the group aggregated value id v once more (LDS: workgroup-private u32 bins, flushed as u64 adds;
   // the planner picks LDS only when no bin can reach 2^32)
   __device__ __forceinline__ void add_hist(const DevAgg& A, int64_t key, int64_t v) const {
-    if (STRAT == STRAT_LDS) atomicAdd((uint32_t*)(lds + A.lds_off) + key * A.nvals + v, 1u);
+    if (acc_in_lds(STRAT)) atomicAdd((uint32_t*)(lds + A.lds_off) + key * A.nvals + v, 1u);
     else __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + key * A.nvals + v, 1ull, RLX);
+  }
+  // filtered aggregations: n more docs of a lane in a group (cell = lane * num_keys + key)
+  __device__ __forceinline__ void add_lane_count(int64_t cell, uint32_t n) const {
+    if (acc_in_lds(STRAT)) atomicAdd((uint32_t*)(lds + q->filt->lds_lane_count_off) + cell, n);
+    else __hip_atomic_fetch_add(gp(q->filt->lane_count) + cell, (unsigned long long)n, RLX);
   }
   __device__ __forceinline__ void max_hll(const DevAgg& A, int64_t key, uint32_t jr) const {
     const int64_t idx = (key << A.log2m) + (jr >> 8);
-    if (STRAT == STRAT_LDS) atomicMax((uint32_t*)(lds + A.lds_off) + idx, jr & 0xffu);
+    if (acc_in_lds(STRAT)) atomicMax((uint32_t*)(lds + A.lds_off) + idx, jr & 0xffu);
     else atomic_max_u8(A.acc_hll + idx, jr & 0xffu);
   }
 };
@@ -356,6 +361,65 @@ __device__ __forceinline__ int64_t key_slot(const DevQuery* __restrict__ q, int6
   }
   if (s < 0) __hip_atomic_fetch_add(gp(q->matched_docs) + 1, 1ull, RLX);
   return s;
+}
+
+// One aggregation's update for one set of lanes of a 64-doc step (`in`: this lane belongs to the set). grouped: the set
+// shares the key k0, so SUM / MIN / MAX are reduced across the wave and lane `leader` updates once; else every lane of
+// the set updates its own `key`. HLL registers, presence bytes and histogram bins are always per lane.
+template <int STRAT>
+__device__ __forceinline__ void agg_update_set(const DevAgg& A, int a, const DevSeg* __restrict__ seg,
+                                               const uint32_t* img, int doc_local, int64_t doc, int64_t key, int64_t k0,
+                                               bool in, bool grouped, int leader, int lane, const Acc<STRAT>& acc) {
+  AggValue v{0, 0.0};
+  if (in) v = agg_value(A, a, seg, img, doc_local, doc);
+  if (A.type == PA_AGG_DISTINCTCOUNTHLL) {
+    if (in) acc.max_hll(A, key, (uint32_t)v.i);
+  } else if (A.type == PA_AGG_DISTINCTCOUNT) {
+    if (in) acc.set_presence(A, key, v.i);
+  } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
+    if (in) acc.add_hist(A, key, v.i);
+  } else if (grouped) {
+    if (A.type == PA_AGG_SUM) {
+      if (A.src == SRC_INT) {
+        const int64_t s = wave_sum_i64(in ? v.i : 0);
+        if (lane == leader) acc.add_i64(A, k0, s);
+      } else if (A.src == SRC_LONG) {
+        const int64_t lo = wave_sum_i64(in ? (int64_t)(uint32_t)v.i : 0);
+        const int64_t hi = wave_sum_i64(in ? (v.i >> 32) : 0);
+        if (lane == leader) {
+          acc.add_i64(A, 2 * k0, lo);
+          acc.add_i64(A, 2 * k0 + 1, hi);
+        }
+      } else {
+        const double s = wave_sum_f64(in ? v.d : 0.0);
+        if (lane == leader) acc.add_f64(A, k0, s);
+      }
+    } else {
+      const int64_t e = A.src != SRC_DOUBLE ? v.i : f64_order_encode(v.d);
+      if (A.type == PA_AGG_MIN) {
+        const int64_t r = wave_min_i64(in ? e : INT64_MAX);
+        if (lane == leader) acc.min_i64(A, k0, r);
+      } else {
+        const int64_t r = wave_max_i64(in ? e : INT64_MIN);
+        if (lane == leader) acc.max_i64(A, k0, r);
+      }
+    }
+  } else if (in) {
+    if (A.type == PA_AGG_SUM) {
+      if (A.src == SRC_INT) {
+        acc.add_i64(A, key, v.i);
+      } else if (A.src == SRC_LONG) {
+        acc.add_i64(A, 2 * key, (int64_t)(uint32_t)v.i);
+        acc.add_i64(A, 2 * key + 1, v.i >> 32);
+      } else {
+        acc.add_f64(A, key, v.d);
+      }
+    } else {
+      const int64_t e = A.src != SRC_DOUBLE ? v.i : f64_order_encode(v.d);
+      if (A.type == PA_AGG_MIN) acc.min_i64(A, key, e);
+      else acc.max_i64(A, key, e);
+    }
+  }
 }
 
 // Accumulate the matched lanes (`matched` = wave mask) of one 64-doc step.
@@ -399,56 +463,7 @@ __device__ __forceinline__ void accumulate_step(const DevQuery* __restrict__ q, 
     for (int a = 0; a < q->num_aggs; ++a) {
       const DevAgg& A = q->aggs[a];
       if (A.type == PA_AGG_COUNT) continue;
-      AggValue v{0, 0.0};
-      if (in) v = agg_value(A, a, seg, img, doc_local, doc);
-      if (A.type == PA_AGG_DISTINCTCOUNTHLL) {
-        if (in) acc.max_hll(A, key, (uint32_t)v.i);
-      } else if (A.type == PA_AGG_DISTINCTCOUNT) {
-        if (in) acc.set_presence(A, key, v.i);
-      } else if (A.type == PA_AGG_VALUE_HISTOGRAM) {
-        if (in) acc.add_hist(A, key, v.i);
-      } else if (grouped) {
-        if (A.type == PA_AGG_SUM) {
-          if (A.src == SRC_INT) {
-            const int64_t s = wave_sum_i64(in ? v.i : 0);
-            if (lane == leader) acc.add_i64(A, k0, s);
-          } else if (A.src == SRC_LONG) {
-            const int64_t lo = wave_sum_i64(in ? (int64_t)(uint32_t)v.i : 0);
-            const int64_t hi = wave_sum_i64(in ? (v.i >> 32) : 0);
-            if (lane == leader) {
-              acc.add_i64(A, 2 * k0, lo);
-              acc.add_i64(A, 2 * k0 + 1, hi);
-            }
-          } else {
-            const double s = wave_sum_f64(in ? v.d : 0.0);
-            if (lane == leader) acc.add_f64(A, k0, s);
-          }
-        } else {
-          const int64_t e = A.src != SRC_DOUBLE ? v.i : f64_order_encode(v.d);
-          if (A.type == PA_AGG_MIN) {
-            const int64_t r = wave_min_i64(in ? e : INT64_MAX);
-            if (lane == leader) acc.min_i64(A, k0, r);
-          } else {
-            const int64_t r = wave_max_i64(in ? e : INT64_MIN);
-            if (lane == leader) acc.max_i64(A, k0, r);
-          }
-        }
-      } else if (in) {
-        if (A.type == PA_AGG_SUM) {
-          if (A.src == SRC_INT) {
-            acc.add_i64(A, key, v.i);
-          } else if (A.src == SRC_LONG) {
-            acc.add_i64(A, 2 * key, (int64_t)(uint32_t)v.i);
-            acc.add_i64(A, 2 * key + 1, v.i >> 32);
-          } else {
-            acc.add_f64(A, key, v.d);
-          }
-        } else {
-          const int64_t e = A.src != SRC_DOUBLE ? v.i : f64_order_encode(v.d);
-          if (A.type == PA_AGG_MIN) acc.min_i64(A, key, e);
-          else acc.max_i64(A, key, e);
-        }
-      }
+      agg_update_set<STRAT>(A, a, seg, img, doc_local, doc, key, k0, in, grouped, leader, lane, acc);
     }
   }
 }
@@ -773,6 +788,46 @@ __device__ __forceinline__ void lds_acc_zero(const DevQuery* q, unsigned char* l
   __syncthreads();
 }
 
+// Key k of one aggregation's workgroup-private LDS accumulators into the global ones (VALUE_HISTOGRAM bins leave in
+// lds_acc_flush's own loop).
+__device__ __forceinline__ void lds_flush_agg(const DevAgg& A, int64_t k, unsigned char* lds_acc) {
+  switch (A.type) {
+    case PA_AGG_SUM:
+      if (A.src == SRC_INT) {
+        __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
+      } else if (A.src == SRC_LONG) {
+        const unsigned long long* r = (const unsigned long long*)(lds_acc + A.lds_off);
+        __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k, r[2 * k], RLX);
+        __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k + 1, r[2 * k + 1], RLX);
+      } else {
+        __hip_atomic_fetch_add(gp(A.acc_f64) + k, ((const double*)(lds_acc + A.lds_off))[k], RLX);
+      }
+      break;
+    case PA_AGG_COUNT_MV:
+      __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
+      break;
+    case PA_AGG_MIN: __hip_atomic_fetch_min(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
+    case PA_AGG_MAX: __hip_atomic_fetch_max(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
+    case PA_AGG_DISTINCTCOUNT: {  // presence words with a value seen here -> bytes of the global block
+      const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off + k * A.nvals);
+      AS1 uint8_t* g = gp(A.acc_hll) + k * A.nvals;
+      for (int64_t j = 0; j < A.nvals / 4; ++j) {
+        const uint32_t w = r[j];
+        if (w == 0) continue;
+        for (int b = 0; b < 4; ++b)
+          if ((w >> (8 * b)) & 0xffu) g[4 * j + b] = 1;
+      }
+    } break;
+    case PA_AGG_DISTINCTCOUNTHLL: {
+      const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off) + (k << A.log2m);
+      uint8_t* g = A.acc_hll + (k << A.log2m);
+      for (int j = 0; j < (1 << A.log2m); ++j)
+        if (r[j] != 0) atomic_max_u8(g + j, r[j]);
+    } break;
+    default: break;
+  }
+}
+
 // STRAT_LDS, end of the kernel: every key the workgroup saw into the global accumulators.
 template <int WGS>
 __device__ __forceinline__ void lds_acc_flush(const DevQuery* q, unsigned char* lds_acc) {
@@ -783,44 +838,7 @@ __device__ __forceinline__ void lds_acc_flush(const DevQuery* q, unsigned char* 
     const uint32_t c = cnt[k];
     if (c == 0) continue;
     __hip_atomic_fetch_add(gp(q->count) + k, (unsigned long long)c, RLX);
-    for (int a = 0; a < q->num_aggs; ++a) {
-      const DevAgg& A = q->aggs[a];
-      switch (A.type) {
-        case PA_AGG_SUM:
-          if (A.src == SRC_INT) {
-            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
-          } else if (A.src == SRC_LONG) {
-            const unsigned long long* r = (const unsigned long long*)(lds_acc + A.lds_off);
-            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k, r[2 * k], RLX);
-            __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 2 * k + 1, r[2 * k + 1], RLX);
-          } else {
-            __hip_atomic_fetch_add(gp(A.acc_f64) + k, ((const double*)(lds_acc + A.lds_off))[k], RLX);
-          }
-          break;
-        case PA_AGG_COUNT_MV:
-          __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + k, ((const unsigned long long*)(lds_acc + A.lds_off))[k], RLX);
-          break;
-        case PA_AGG_MIN: __hip_atomic_fetch_min(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
-        case PA_AGG_MAX: __hip_atomic_fetch_max(gp((long long*)A.acc_i64) + k, ((const long long*)(lds_acc + A.lds_off))[k], RLX); break;
-        case PA_AGG_DISTINCTCOUNT: {  // presence words with a value seen here -> bytes of the global block
-          const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off + k * A.nvals);
-          AS1 uint8_t* g = gp(A.acc_hll) + k * A.nvals;
-          for (int64_t j = 0; j < A.nvals / 4; ++j) {
-            const uint32_t w = r[j];
-            if (w == 0) continue;
-            for (int b = 0; b < 4; ++b)
-              if ((w >> (8 * b)) & 0xffu) g[4 * j + b] = 1;
-          }
-        } break;
-        case PA_AGG_DISTINCTCOUNTHLL: {
-          const uint32_t* r = (const uint32_t*)(lds_acc + A.lds_off) + (k << A.log2m);
-          uint8_t* g = A.acc_hll + (k << A.log2m);
-          for (int j = 0; j < (1 << A.log2m); ++j)
-            if (r[j] != 0) atomic_max_u8(g + j, r[j]);
-        } break;
-        default: break;
-      }
-    }
+    for (int a = 0; a < q->num_aggs; ++a) lds_flush_agg(q->aggs[a], k, lds_acc);
   }
   // VALUE_HISTOGRAM: a row can hold tens of thousands of bins, so the workgroup's threads walk the bins of all keys
   // (not one thread per key): every non-zero u32 bin becomes one u64 add into the global block
@@ -3115,6 +3133,185 @@ __device__ __forceinline__ void distinct_lds_flush(const DevQuery* q, unsigned c
   }
 }
 
+// ---------------------------------------------------------------- filtered aggregations (STRAT_FILTERED_LDS / STRAT_FILTERED)
+// AGG(x) FILTER (WHERE F_j): the reference runs one filter + projection + executor per "swim lane"
+// (FilteredAggregationOperator.java:66-101, FilteredGroupByOperator.java:107-200: a walk over the segment per lane).
+// Here the columns stream once: after the query's own filter W left the tile's survivors m, every lane's CNF (FiltDesc)
+// gives m_j = m & F_j — literals on staged dictionary columns on the whole tile (leaf_bits), the others per surviving
+// doc (leaf_match_doc) — and the group key is computed once per doc of the lanes' union u (the shared group-key
+// generator, FilteredGroupByOperator.java:117-150: a group exists when any lane saw a doc of it; the group count
+// counts u). Lane j then accumulates its aggregations and its doc count (PA_ACC_LANE_COUNT_U64) under its own mask
+// with accumulate_step's wave pre-reduction; aggregations without a filter run under m (the main lane). Per segment
+// the docs of W and of every lane are counted by popcount (the execution statistics' input).
+//   STRAT_FILTERED_LDS: group counts, lane counts and every aggregation workgroup-private in LDS (the STRAT_LDS layout
+//     + u32 lane counts), flushed once per workgroup: one global atomic per cell of a lane that saw the key.
+//   STRAT_FILTERED: device-scope atomics per pre-reduced set.
+// Direct key spaces and single-value columns only (pa_query_prepare refuses the rest), step-major tiles.
+
+// Lane mask of one CNF (n literals, clause-major) over the tile's surviving docs m.
+template <int STEPS>
+__device__ __forceinline__ uint32_t filt_lane_mask(const DevLeaf* lits, int n, const uint32_t* img, int64_t doc_base,
+                                                   uint32_t m, int lane) {
+  uint32_t mj = m, clause = 0;
+  for (int li = 0; li < n; ++li) {
+    const DevLeaf& L = lits[li];
+    uint32_t bits = 0;
+    if ((L.kind == PA_LEAF_DICT_RANGE || L.kind == PA_LEAF_DICT_SET) && L.lds_off >= 0) {
+      bits = leaf_bits<STEPS>(L, img, doc_base, lane);
+    } else {
+      // not staged (or a raw column): only docs that can still change the lane's mask, each a doc of the segment
+      const uint32_t todo = mj & ~clause;
+      for (int i = 0; i < STEPS; ++i) {
+        if (__ballot((todo >> i) & 1u) == 0) continue;
+        if ((todo >> i) & 1u) bits |= (uint32_t)leaf_match_doc(L, doc_base + i * kWave + lane) << i;
+      }
+    }
+    clause |= bits;
+    if (L.clause_end) {
+      mj &= clause;
+      clause = 0;
+    }
+  }
+  return mj & m;  // (a negated leaf sets bits past the segment's last doc: process_tile)
+}
+
+// Lane j's mask out of the four pairs filtered_tile keeps (values, not references: a conditional between two lvalues
+// selects an address, and the masks would have to live in memory).
+__device__ __forceinline__ uint32_t filt_pair_mask(uint64_t p0, uint64_t p1, uint64_t p2, uint64_t p3, int j) {
+  const uint64_t k = (uint64_t)(j >> 1);
+  const uint64_t p = (p0 & (0ull - (uint64_t)(k == 0))) | (p1 & (0ull - (uint64_t)(k == 1))) |
+                     (p2 & (0ull - (uint64_t)(k == 2))) | (p3 & (0ull - (uint64_t)(k == 3)));
+  return (uint32_t)(p >> ((j & 1) * 32));
+}
+
+// One lane's docs of one 64-doc step (`set_mask`: wave mask) into the lane's doc count and aggregations: the equal-key
+// sets of accumulate_step. cell0 < 0: the count is the group's (Acc::add_count), else the lane count at cell0 + key.
+template <int STRAT>
+__device__ __forceinline__ void filtered_lane_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                                   const uint32_t* img, int doc_local, int64_t doc, int64_t key,
+                                                   uint64_t set_mask, int lane, const Acc<STRAT>& acc,
+                                                   const int32_t* aggs, int naggs, int64_t cell0) {
+  uint64_t pending = set_mask;
+  bool first = true;
+  while (pending) {
+    const int leader = __builtin_ctzll(pending);
+    const int64_t k0 = __shfl(key, leader);
+    const uint64_t same = __ballot(key == k0) & pending;
+    const bool grouped = !first || (__builtin_popcountll(same) * 4 >= __builtin_popcountll(pending));
+    first = false;
+    const uint64_t set = grouped ? same : pending;
+    pending &= ~set;
+    const bool in = (set >> lane) & 1ull;
+    if (grouped) {
+      if (lane == leader) {
+        if (cell0 < 0) acc.add_count(k0, (uint32_t)__builtin_popcountll(set));
+        else acc.add_lane_count(cell0 + k0, (uint32_t)__builtin_popcountll(set));
+      }
+    } else if (in) {
+      if (cell0 < 0) acc.add_count(key, 1u);
+      else acc.add_lane_count(cell0 + key, 1u);
+    }
+    for (int x = 0; x < naggs; ++x) {
+      const int a = aggs[x];
+      agg_update_set<STRAT>(q->aggs[a], a, seg, img, doc_local, doc, key, k0, in, grouped, leader, lane, acc);
+    }
+  }
+}
+
+// The docs of one tile that passed W (bit i of m: the lane's doc of step i): lane masks, counters, aggregation.
+template <int STRAT, int STEPS>
+__device__ __forceinline__ void filtered_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                              const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
+                                              const Acc<STRAT>& acc) {
+  const FiltDesc* __restrict__ F = uniform_ptr(q->filt);
+  const int NL = F->num_lanes;
+  const bool has_main = F->has_main != 0;
+  const DevLeaf* lits = uniform_ptr(F->leaves + (int64_t)seg->index * F->num_lits);
+  // the lanes' masks, two to a 64-bit scalar (lane j: bits 32 (j & 1) .. of pair j >> 1). Named scalars, not an array:
+  // an array indexed by the lane number stays in scratch memory, whose loads and stores wait behind the DMA ring.
+  static_assert(PA_MAX_AGG_FILTERS == 8 && STEPS <= 32, "four pairs of 32-bit lane masks");
+  uint64_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;
+  uint32_t u = has_main ? m : 0u;
+  for (int j = 0; j < NL; ++j) {
+    const int b = F->lit_begin[j];
+    const uint32_t mj = filt_lane_mask<STEPS>(lits + b, F->lit_begin[j + 1] - b, img, doc_base, m, lane);
+    const uint64_t w = (uint64_t)mj << ((j & 1) * 32);
+    p0 |= (j >> 1) == 0 ? w : 0ull;
+    p1 |= (j >> 1) == 1 ? w : 0ull;
+    p2 |= (j >> 1) == 2 ? w : 0ull;
+    p3 |= (j >> 1) == 3 ? w : 0ull;
+    u |= mj;
+  }
+  AS1 unsigned long long* sd = gp(F->seg_docs) + (int64_t)seg->index * (NL + 1);
+  {
+    const int64_t w = wave_sum_i64((int64_t)__builtin_popcount(m));
+    if (lane == 0 && w != 0) __hip_atomic_fetch_add(sd, (unsigned long long)w, RLX);
+  }
+  for (int j = 0; j < NL; ++j) {
+    const int64_t c = wave_sum_i64((int64_t)__builtin_popcount(filt_pair_mask(p0, p1, p2, p3, j)));
+    if (lane == 0 && c != 0) __hip_atomic_fetch_add(sd + 1 + j, (unsigned long long)c, RLX);
+  }
+  if (__ballot(u != 0) == 0) return;
+  const int64_t K = q->num_keys;
+  for (int i = 0; i < STEPS; ++i) {
+    const uint64_t um = __ballot((u >> i) & 1u);
+    if (um == 0) continue;
+    const int doc_local = i * kWave + lane;
+    const int64_t doc = doc_base + doc_local;
+    int64_t key = 0;
+    if ((um >> lane) & 1ull)
+      for (int j = 0; j < q->num_gb; ++j)
+        key += (int64_t)(gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc) *
+                         (uint64_t)q->gb_stride[j]);
+    // the group count under the union, with the main lane's aggregations when there is one (then u == m)
+    filtered_lane_step<STRAT>(q, seg, img, doc_local, doc, key, um, lane, acc, F->lane_aggs[NL],
+                              has_main ? F->lane_naggs[NL] : 0, -1);
+    for (int j = 0; j < NL; ++j) {
+      const uint64_t jm = __ballot((filt_pair_mask(p0, p1, p2, p3, j) >> i) & 1u);
+      if (jm == 0) continue;
+      filtered_lane_step<STRAT>(q, seg, img, doc_local, doc, key, jm, lane, acc, F->lane_aggs[j], F->lane_naggs[j],
+                                (int64_t)j * K);
+    }
+  }
+}
+
+// STRAT_FILTERED_LDS, start of the kernel: the workgroup's lane counts to zero, then the STRAT_LDS accumulators.
+template <int WGS>
+__device__ __forceinline__ void filtered_lds_zero(const DevQuery* q, unsigned char* lds_acc) {
+  const FiltDesc* F = q->filt;
+  uint32_t* lc = (uint32_t*)(lds_acc + F->lds_lane_count_off);
+  const int64_t n = (int64_t)F->num_lanes * q->num_keys;
+  for (int64_t k = threadIdx.x; k < n; k += WGS) lc[k] = 0u;
+  lds_acc_zero<WGS>(q, lds_acc);
+}
+
+// STRAT_FILTERED_LDS, end of the kernel: for every key the workgroup saw, the group count, and for every lane that saw
+// it the lane count and that lane's aggregations (the cells of the other lanes hold identities: nothing to send).
+template <int WGS>
+__device__ __forceinline__ void filtered_lds_flush(const DevQuery* q, unsigned char* lds_acc) {
+  __syncthreads();
+  const FiltDesc* F = q->filt;
+  const int64_t K = q->num_keys;
+  const int NL = F->num_lanes;
+  const uint32_t* cnt = (const uint32_t*)(lds_acc + q->lds_count_off);
+  const uint32_t* lc = (const uint32_t*)(lds_acc + F->lds_lane_count_off);
+  for (int64_t k = threadIdx.x; k < K; k += WGS) {
+    const uint32_t c = cnt[k];
+    if (c == 0) continue;
+    __hip_atomic_fetch_add(gp(q->count) + k, (unsigned long long)c, RLX);
+    for (int j = 0; j <= NL; ++j) {
+      if (j < NL) {
+        const uint32_t n = lc[(int64_t)j * K + k];
+        if (n == 0) continue;
+        __hip_atomic_fetch_add(gp(F->lane_count) + (int64_t)j * K + k, (unsigned long long)n, RLX);
+      } else if (!F->has_main) {
+        break;
+      }
+      for (int x = 0; x < F->lane_naggs[j]; ++x) lds_flush_agg(q->aggs[F->lane_aggs[j][x]], k, lds_acc);
+    }
+  }
+}
+
 // The rare part of a tile (some doc survived the eager clauses): lazy clauses per surviving doc, then aggregation.
 // Returns the docs that matched.
 // LM: doc of bit i of lane l = 32l + i (lane-major tile), else 64i + l.
@@ -3162,6 +3359,9 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
     select_tile<STEPS, LM>(q, seg, img, doc_base, m, lane, la);
   } else if constexpr (is_distinct(STRAT)) {
     distinct_tile<STRAT, STEPS, LM>(q, seg, img, doc_base, m, lane, lds);
+  } else if constexpr (is_filtered(STRAT)) {
+    static_assert(!LM, "filtered aggregations run step-major tiles");
+    filtered_tile<STRAT, STEPS>(q, seg, img, doc_base, m, lane, acc);
   } else if constexpr (is_lane(STRAT)) {
     if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_tile<LM, STEPS, STRAT>(q, seg, img, doc_base, m, lane, la, lds);
   } else if constexpr (is_pcount(STRAT) || is_pemit(STRAT)) {
@@ -3493,6 +3693,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (is_lane(STRAT) && STRAT != STRAT_LANE_CNT) lane_acc_init(q, la, smem, WGS);
   if constexpr (STRAT == STRAT_SELECT) sel_state_init(la, smem, wave);
   if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_zero<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_zero<WGS>(q, lds_acc);
   const int64_t T = q->total_wtiles;
   const int64_t W = (int64_t)gridDim.x * WPW;
@@ -3647,6 +3848,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
     }
   if constexpr (STRAT == STRAT_SELECT) sel_counters_flush(q, la, lane);
   if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_flush<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_flush<WGS>(q, lds_acc);
   if (!is_pemit(STRAT)) {  // (the partitioned count pass counts numDocsScanned; its emit pass sees the same docs)
     const int64_t wm = wave_sum_i64((int64_t)matched);
     if (lane == 0 && wm != 0) __hip_atomic_fetch_add(gp(q->matched_docs), (unsigned long long)wm, RLX);
@@ -3675,5 +3877,6 @@ const void* scan_fn_part_mv(int strategy);                 // pa_scan_part_mv.hi
 const void* scan_fn_gdense(int strategy, int lm);          // pa_scan_gdense.hip: STRAT_GDENSE (pa_gdense.h)
 const void* scan_fn_select(int strategy, int steps);       // pa_scan_select.hip: STRAT_SELECT (step-major tiles)
 const void* scan_fn_distinct(int strategy, int steps);     // pa_scan_distinct.hip: STRAT_DISTINCT* (step-major tiles)
+const void* scan_fn_filtered(int strategy, int steps);     // pa_scan_filtered.hip: STRAT_FILTERED* (step-major tiles)
 
 }  // namespace pa

@@ -71,7 +71,11 @@
   X(select_cap, -1, 2, 131072, 0)                                                                                      \
   /* distinct (STRAT_DISTINCT_LDS): 0 = never the workgroup-private LDS bitmap, 1 = the planner's choice (default:    \
      the LDS bitmap when it fits next to the tile ring without costing resident workgroups), 2 = whenever it fits */   \
-  X(distinct_lds, 1, 0, 2, 0)
+  X(distinct_lds, 1, 0, 2, 0)                                                                                          \
+  /* filtered aggregations: 0 = device-scope atomics (STRAT_FILTERED), 1 = the workgroup-private LDS accumulators       \
+     (STRAT_FILTERED_LDS) whenever they fit next to a tile ring (default: when they take at most 64 KiB and the lanes'  \
+     union is dense, STRAT_LDS's rule) */                                                                               \
+  X(filtered_lds, -1, 0, 1, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;

@@ -332,16 +332,56 @@ class GpuQueryExecutor:
         # *MV forms aggregate every value of a multi-value column)
         self.pa_aggs = []
         self.agg_map = []
+        # aggregation filters (AGG(x) FILTER (WHERE f)): one lane per distinct filter as written — the reference keys
+        # its swim lanes by FilterContext (AggregationFunctionUtils.java:340-373), and QueryOptimizer.optimize
+        # (QueryOptimizer.java:59-75) rewrites only the WHERE expression, never a FILTER clause, so no merge of ranges
+        # or IN lists happens here either; only constants are folded. lane_dev[k]: the library's filter index of lane k,
+        # or "all" (the filter folds to TRUE: its aggregations run in the main lane) / "none" (FALSE: a lane without docs,
+        # its aggregations keep their empty values and never reach the GPU).
+        self.lane_filters, self.lane_dev, self.dev_filters = [], [], []
+        self.pa_agg_filter = []   # per GPU accumulator: the library's filter index, -1 = the main lane
+        self.agg_lane = []        # per query aggregation: its lane (index into lane_filters), -1 = no filter
+        acc_keys = []
+
+        def lane_of(a):
+            if a.filter is None:
+                return -1
+            if a.filter not in self.lane_filters:
+                f = _fold_constants(a.filter)
+                if _has_comparison(f):
+                    raise UnsupportedQuery("comparison between two different columns in an aggregation filter")
+                if isinstance(f, Q.BoolFilter):
+                    dev = "all" if f.value else "none"
+                else:
+                    if len(self.dev_filters) == L.PA_MAX_AGG_FILTERS:
+                        raise UnsupportedQuery("more than %d aggregation filters in one query" % L.PA_MAX_AGG_FILTERS)
+                    self.dev_filters.append(f)
+                    dev = len(self.dev_filters) - 1
+                self.lane_filters.append(a.filter)
+                self.lane_dev.append(dev)
+            return self.lane_filters.index(a.filter)
+
+        cur = [-1]  # the library's filter index of the aggregation being mapped
 
         def acc_index(key):
-            if key not in self.pa_aggs:
+            ident = key + (cur[0],)
+            if ident not in acc_keys:
+                acc_keys.append(ident)
                 self.pa_aggs.append(key)
-            return self.pa_aggs.index(key)
+                self.pa_agg_filter.append(cur[0])
+            return acc_keys.index(ident)
 
         for a in q.aggregations:
             fn = a.function
             if fn.endswith("MV") and seg0.column(a.column).single_value:
                 raise UnsupportedQuery("%s on single-value column %s" % (fn, a.column))
+            lane = lane_of(a)
+            self.agg_lane.append(lane)
+            dev = self.lane_dev[lane] if lane >= 0 else "all"
+            if dev == "none":
+                self.agg_map.append(None)  # (fetch fills in the function's empty value)
+                continue
+            cur[0] = -1 if dev == "all" else dev
             if fn == "COUNT":
                 self.agg_map.append(acc_index((L.PA_AGG_COUNT, -1, 0)))
             elif fn == "AVGMV":
@@ -374,6 +414,10 @@ class GpuQueryExecutor:
                 self.agg_map.append(acc_index((L.PA_AGG_VALUE_HISTOGRAM, ids[a.column], 0)))
             else:
                 raise UnsupportedQuery("aggregation %s" % fn)
+        if q.aggregations and all(m is None for m in self.agg_map):
+            self.match_none = True  # every aggregation's filter is FALSE: no lane sees a doc, so no group exists
+            self.pa_aggs.append((L.PA_AGG_COUNT, -1, 0))  # (the block's layout only: nothing is scanned)
+            self.pa_agg_filter.append(-1)
         if len(self.pa_aggs) > L.PA_MAX_AGGS:
             raise UnsupportedQuery("too many aggregations")
         spec.num_aggs = len(self.pa_aggs)
@@ -403,8 +447,17 @@ class GpuQueryExecutor:
         leaves, ops = [], []
         if filt is not None:
             _flatten_filter(filt, leaves, ops)
-        if len(leaves) > L.PA_MAX_LEAVES or len(ops) > L.PA_MAX_OPS:
-            raise UnsupportedQuery("filter too large")
+        # the aggregation filters' leaves follow the main filter's (pa_query_set_agg_filters): bound per segment below
+        # like any other leaf; each filter has its own postfix program
+        self.dev_filter_ops = []
+        for f in self.dev_filters:
+            fops = []
+            _flatten_filter(f, leaves, fops)
+            self.dev_filter_ops.append(fops)
+        if len(leaves) > L.PA_MAX_LEAVES or len(ops) > L.PA_MAX_OPS or any(len(o) > L.PA_MAX_OPS for o in self.dev_filter_ops):
+            raise UnsupportedQuery("filter too large" if not self.dev_filters else
+                                   "filters too large: the WHERE and the aggregation filters hold more than %d leaves "
+                                   "together, or one of them more than %d operations" % (L.PA_MAX_LEAVES, L.PA_MAX_OPS))
         per_seg = []
         for seg in self.segs:
             params = []
@@ -483,6 +536,16 @@ class GpuQueryExecutor:
             L.check(lib.pa_query_set_tuning(self.handle, name.encode(), int(value)), "pa_query_set_tuning")
         self._keep = []
         self._after_create()
+        if self.dev_filters:
+            fs = L.AggFilterSpec()
+            fs.num_filters = len(self.dev_filters)
+            for j, fops in enumerate(self.dev_filter_ops):
+                fs.num_ops[j] = len(fops)
+                for i, op in enumerate(fops):
+                    fs.ops[j][i] = op
+            for i in range(L.PA_MAX_AGGS):
+                fs.agg_filter[i] = self.pa_agg_filter[i] if i < len(self.pa_agg_filter) else -1
+            L.check(lib.pa_query_set_agg_filters(self.handle, ctypes.byref(fs)), "pa_query_set_agg_filters")
         for si, (g, params) in enumerate(zip(self.gsegs, per_seg)):
             arr = (L.LeafParams * max(1, len(params)))()
             for li, p in enumerate(params):
@@ -522,7 +585,12 @@ class GpuQueryExecutor:
                 self._keep.append(rm)
                 L.check(lib.pa_query_bind_value_remap(self.handle, si, i, rm.ctypes.data), "pa_query_bind_value_remap")
         self._before_prepare()
-        L.check(lib.pa_query_prepare(self.handle), "pa_query_prepare")
+        try:
+            L.check(lib.pa_query_prepare(self.handle), "pa_query_prepare")
+        except L.PinotAmdError as e:
+            if self.dev_filters and getattr(e, "code", 0) == L.PA_EUNSUPPORTED:
+                raise UnsupportedQuery(str(e)) from None  # (what the library refuses of a filtered-aggregation query)
+            raise
         self.num_keys = int(lib.pa_query_num_keys(self.handle))
         hashed, shifts = ctypes.c_int32(), (ctypes.c_int32 * max(1, len(q.group_by)))()
         L.check(lib.pa_query_key_layout(self.handle, ctypes.byref(hashed), shifts), "pa_query_key_layout")
@@ -590,7 +658,7 @@ class GpuQueryExecutor:
         out["plan"]["strategy"] = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane", 6: "lane", 7: "lane",
                                     8: "lds_dense", 9: "lds_dense", 10: "lds_dense", 11: "lds_dense", 12: "lds_dense",
                                     14: "lds_dense", 15: "lds_dense", 128: "select", 129: "distinct",
-                                    130: "distinct"}[code]
+                                    130: "distinct", 131: "filtered", 132: "filtered"}[code]
         out["plan"]["variant"] = STRATEGY_VARIANTS.get(code, str(code))
         out["plan"]["eager_literals"] = int(L.lib().pa_query_num_eager_literals(self.handle))
         out["plan"]["lane_major"] = int(L.lib().pa_query_lane_major(self.handle))
@@ -642,6 +710,62 @@ class GpuQueryExecutor:
                 (o[: n * self._presence_stride(i)] if self.pa_aggs[i][0] == L.PA_AGG_DISTINCTCOUNT else o[:n])
                 for i, o in enumerate(outs)]
         return (keys[:n] if kw == 1 else keys[:2 * n].reshape(n, 2)), counts[:n], outs
+
+    def fetch_lane_counts(self, num_groups, stream=None):
+        """int64[filters, num_groups]: the docs of every aggregation filter's lane (W AND F_j) in the groups the last
+        fetch_arrays returned, in its order (pa_query_fetch_lane_counts). Synchronises `stream`."""
+        nf = len(self.dev_filters)
+        out = np.zeros((nf, max(int(num_groups), 1)), dtype=np.int64)[:, :int(num_groups)]
+        out = np.ascontiguousarray(out)
+        if nf and num_groups:
+            L.check(L.lib().pa_query_fetch_lane_counts(self.handle, stream, int(num_groups), out.ctypes.data),
+                    "pa_query_fetch_lane_counts")
+        return out
+
+    def lane_docs(self, stream=None):
+        """int64[segments, 1 + filters]: per bound segment the docs matching the query's filter W, then W AND F_j for
+        every aggregation filter (pa_query_lane_docs), of the last scan. After a fetch the library hands out the
+        counters that fetch read (no further synchronisation). A query whose FILTER clauses all folded to constants
+        has no lane on the device: its scan counted W's docs over all segments together (pa_query_matched_docs), so
+        W's docs per segment are the segment's docs (no WHERE), that total (one segment), or the WHERE's mask over
+        the GPU's leaf bitmaps (synchronises `stream`)."""
+        out = np.zeros((len(self.segs), 1 + len(self.dev_filters)), dtype=np.int64)
+        if not self.segs or self.match_none or self.handle is None or not getattr(self, "_scanned", False):
+            return out
+        if self.dev_filters:
+            L.check(L.lib().pa_query_lane_docs(self.handle, out.ctypes.data), "pa_query_lane_docs")
+        elif self.lane_filters:
+            from . import filter_stats as FS
+            if self.query.filter is None:
+                out[:, 0] = [seg.num_docs for seg in self.segs]
+            elif len(self.segs) == 1:
+                out[0, 0] = int(L.lib().pa_query_matched_docs(self.handle))
+            else:
+                for si, seg in enumerate(self.segs):
+                    out[si, 0] = int(FS.filter_mask(self.query.filter, seg, self.leaf_bitmaps(si, stream)).sum())
+        return out
+
+    def filtered_stats(self, stream=None):
+        """(numDocsScanned, numEntriesScannedPostFilter) of a query with aggregation filters: per segment, the sum
+        over that segment's swim lanes (filter_stats.lane_structure) of the lane's docs, and of docs x the columns the
+        lane projects (FilteredAggregationOperator.java:96-98, FilteredGroupByOperator.java:159-161)."""
+        from . import filter_stats as FS
+        q = self.query
+        docs = self.lane_docs(stream)
+        scanned = post = 0
+        for si, seg in enumerate(self.segs):
+            w = int(docs[si, 0])
+            for f, aggs in FS.lane_structure(q, seg):
+                if f is None:
+                    n = w
+                elif isinstance(f, str):   # ("empty": the main filter matches nothing here)
+                    n = 0
+                else:
+                    dev = self.lane_dev[self.lane_filters.index(f)]
+                    n = w if dev == "all" else (0 if dev == "none" else int(docs[si, 1 + dev]))
+                scanned += n
+                post += n * FS.lane_projected_columns(q, aggs)
+        return scanned, post
 
     def _presence_stride(self, i):
         """DISTINCTCOUNT presence bytes per group: the value count rounded up to 16 (PA_ACC_PRESENCE_U8)."""
@@ -812,7 +936,25 @@ class GpuQueryExecutor:
         res.num_total_docs = sum(s.num_docs for s in self.all_segs)
         res.num_docs_scanned = int(lib.pa_query_matched_docs(self.handle))
         merged = getattr(self, "merged_stats", None)
-        if merged is not None:
+        filtered = bool(self.lane_filters)
+        if filtered and merged is not None and not isinstance(merged, str):
+            raise L.PinotAmdError("a query with aggregation filters has no merged execution statistics")
+        if filtered and merged is None:
+            # numDocsScanned and numEntriesScannedPostFilter are sums over the swim lanes; numEntriesScannedInFilter is
+            # not defined here: CombinedFilterOperator.java:62-67 turns the main filter into a bitmap through
+            # BlockDocIdSet.toNonScanDocIdSet, whose scan is not counted (BlockDocIdSet.java:57-58)
+            # (the lanes' per-segment docs came with fetch_arrays' own copy: no second synchronisation)
+            res.num_docs_scanned, post = self.filtered_stats(stream)
+            res.num_entries_scanned_in_filter = None
+            res.num_entries_scanned_post_filter = post if execution_stats else 0
+        elif filtered:
+            # (summed across GPUs: the lanes' per-segment docs of the other ranks are not here)
+            res.num_docs_scanned = None
+            res.num_entries_scanned_in_filter = None
+            if execution_stats:
+                raise L.PinotAmdError("the merged block of a query with aggregation filters has no execution "
+                                      "statistics: fetch(execution_stats=False)")
+        elif merged is not None:
             # numDocsScanned was summed across GPUs (parallel.DistributedAccumulators.reduce): this rank's segments
             # cannot recount the statistics against it; the reduce summed every rank's own pair before its collective
             # (reduce(execution_stats=True), the default), or gathered none (NO_MERGED_STATS)
@@ -827,7 +969,22 @@ class GpuQueryExecutor:
         key_cols = [kc.tolist() for kc in self.key_values(keys)]
         cols = []  # one python list per query aggregation
         hists = {}
-        for a, pi in zip(q.aggregations, self.agg_map):
+        lane_counts = self.fetch_lane_counts(n, stream) if self.dev_filters and not self.match_none else None
+        group_counts = counts
+        for ai, (a, pi) in enumerate(zip(q.aggregations, self.agg_map)):
+            # the docs behind this aggregation: its lane's (a filtered aggregation) or the group's
+            dev = self.lane_dev[self.agg_lane[ai]] if self.agg_lane[ai] >= 0 else "all"
+            if dev == "none" or (self.match_none and filtered):
+                cols.append([_empty_value(a) for _ in range(n)])  # a lane without docs
+                continue
+            counts = group_counts if dev == "all" else lane_counts[dev]
+            if dev != "all" and a.function in ("MIN", "MAX", "MINMAXRANGE"):
+                # a group its lane saw no doc of holds the accumulators' reset values: the functions' empty results
+                seen = counts > 0
+                for p_, empty in zip(pi if isinstance(pi, tuple) else (pi,),
+                                     (np.inf, -np.inf) if a.function == "MINMAXRANGE" else
+                                     ((np.inf,) if a.function == "MIN" else (-np.inf,))):
+                    outs[p_] = np.where(seen, outs[p_], empty)
             if a.function == "COUNT":
                 cols.append(counts.tolist())
             elif a.function == "AVG":
@@ -875,16 +1032,7 @@ class GpuQueryExecutor:
         q = self.query
         res = IntermediateResult(list(q.aggregations), list(q.group_by))
         if not q.group_by:
-            row = []
-            for a in q.aggregations:
-                fn = Q.base_function(a.function)
-                row.append({"COUNT": 0, "SUM": 0.0, "MIN": float("inf"), "MAX": float("-inf")}.get(fn) if fn in
-                           ("COUNT", "SUM", "MIN", "MAX") else
-                           AvgPair(0.0, 0) if fn == "AVG" else
-                           HyperLogLog(a.log2m) if fn in ("DISTINCTCOUNTHLL", "DISTINCTCOUNTRAWHLL") else
-                           MinMaxRangePair(float("inf"), float("-inf")) if fn == "MINMAXRANGE" else
-                           ValueHistogram() if fn == "PERCENTILE" else set())
-            res.row = row
+            res.row = [_empty_value(a) for a in q.aggregations]
         return res
 
     def run(self, stream=None) -> IntermediateResult:
@@ -909,7 +1057,8 @@ class GpuQueryExecutor:
 # the kernel variant behind each pa_query_plan strategy code (pa_device.h Strategy)
 STRATEGY_VARIANTS = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane_cnt", 6: "lane_raw", 7: "lane_dict",
                      8: "gdense4", 9: "gdense8", 10: "gdense12", 11: "gdense_rs12", 12: "gdense_rs8", 14: "gdense_lm8",
-                     15: "gdense_lm16", 128: "select", 129: "distinct_lds", 130: "distinct_global"}
+                     15: "gdense_lm16", 128: "select", 129: "distinct_lds", 130: "distinct_global",
+                     131: "filtered_lds", 132: "filtered_global"}
 
 
 class SelectionExecutor(GpuQueryExecutor):
@@ -1191,6 +1340,38 @@ class DistinctExecutor(GpuQueryExecutor):
     def run(self, stream=None):
         self.execute(stream)
         return self.fetch(stream)
+
+
+def _empty_value(a):
+    """An aggregation function's intermediate result over no docs."""
+    fn = Q.base_function(a.function)
+    return ({"COUNT": 0, "SUM": 0.0, "MIN": float("inf"), "MAX": float("-inf")}.get(fn) if fn in
+            ("COUNT", "SUM", "MIN", "MAX") else
+            AvgPair(0.0, 0) if fn == "AVG" else
+            HyperLogLog(a.log2m) if fn in ("DISTINCTCOUNTHLL", "DISTINCTCOUNTRAWHLL") else
+            MinMaxRangePair(float("inf"), float("-inf")) if fn == "MINMAXRANGE" else
+            ValueHistogram() if fn == "PERCENTILE" else set())
+
+
+def _fold_constants(f):
+    """A filter tree with its TRUE / FALSE literals folded away (AND / OR / NOT over constants, as FilterPlanNode folds
+    MatchAll / Empty operators): a BoolFilter when the whole tree is constant."""
+    if isinstance(f, (Q.And, Q.Or)):
+        is_and = isinstance(f, Q.And)
+        kids = []
+        for c in (_fold_constants(c) for c in f.children):
+            if isinstance(c, Q.BoolFilter):
+                if c.value != is_and:   # FALSE in an AND, TRUE in an OR: the whole node
+                    return c
+                continue
+            kids.append(c)
+        if not kids:
+            return Q.BoolFilter(is_and)
+        return kids[0] if len(kids) == 1 else type(f)(tuple(kids))
+    if isinstance(f, Q.Not):
+        c = _fold_constants(f.child)
+        return Q.BoolFilter(not c.value) if isinstance(c, Q.BoolFilter) else Q.Not(c)
+    return f
 
 
 def _has_comparison(f):

@@ -490,6 +490,68 @@ def projected_columns(query):
     return len(cols)
 
 
+def filter_constant(filt, segment):
+    """"all" / "empty" when FilterPlanNode folds the filter to a MatchAllFilterOperator / EmptyFilterOperator in this
+    segment (constant predicates by the segment's dictionaries, _leaf_op; AND / OR / NOT over them, _build), else
+    None. No filter is "all"."""
+    if filt is None:
+        return "all"
+    info = segment_index_info(segment)
+
+    def kind(f):
+        if isinstance(f, Q.BoolFilter):
+            return "all" if f.value else "empty"
+        if isinstance(f, (Q.And, Q.Or)):
+            ks = [kind(c) for c in f.children]
+            whole, unit = ("empty", "all") if isinstance(f, Q.And) else ("all", "empty")
+            return whole if whole in ks else (unit if all(k == unit for k in ks) else None)
+        if isinstance(f, Q.Not):
+            return {"all": "empty", "empty": "all"}.get(kind(f.child))
+        try:
+            k = _leaf_op(f, segment, None, info).kind
+        except _Unsupported:
+            return None
+        return k if k in ("all", "empty") else None
+    return kind(filt)
+
+
+def lane_structure(query, segment):
+    """The swim lanes of a query with filtered aggregations in one segment, as
+    AggregationFunctionUtils.buildFilteredAggregationInfos builds them (:312-396): [(filter, [aggregations])] with
+    filter = the FILTER clause's tree as written (the lane's docs match WHERE AND filter), None for the main lane (the
+    WHERE alone), or "empty" for the single lane of a segment whose main filter is empty (:321-329). Aggregations with
+    an equal filter share a lane (:340-373); a sub filter that is match-all here, under a main filter that is neither
+    match-all nor empty, runs on the main operator itself and joins the main lane (:353-354, :376-378) — under a
+    match-all main filter the combined operator is the sub filter's own (:351-352), so it stays a lane."""
+    main = filter_constant(query.filter, segment)
+    if main == "empty":
+        return [("empty", list(query.aggregations))]
+    lanes, non_filtered = {}, []
+    for a in query.aggregations:
+        if a.filter is None:
+            non_filtered.append(a)
+        else:
+            lanes.setdefault(a.filter, []).append(a)
+    out = []
+    for f, aggs in lanes.items():
+        if main != "all" and filter_constant(f, segment) == "all":
+            non_filtered += aggs
+        else:
+            out.append((f, aggs))
+    if non_filtered:
+        out.append((None, non_filtered))
+    return out
+
+
+def lane_projected_columns(query, aggregations):
+    """Columns one lane's ProjectionOperator reads: the group-by columns and its aggregations' arguments."""
+    cols = list(query.group_by)
+    for a in aggregations:
+        if a.column is not None and a.column not in cols:
+            cols.append(a.column)
+    return len(cols)
+
+
 def server_stats(query, segments, leaf_bitmaps):
     """(numEntriesScannedInFilter, numEntriesScannedPostFilter) of one server's segments. leaf_bitmaps(i) -> bool[leaves,
     num_docs] of segment i in the engine's leaf order (GpuQueryExecutor.leaf_bitmaps)."""

@@ -26,6 +26,7 @@ SECTION_OP = {
     L.PA_ACC_DOCS_U64: dist.ReduceOp.SUM,
     L.PA_ACC_PRESENCE_U8: dist.ReduceOp.MAX,  # DISTINCTCOUNT value presence bytes (set union)
     L.PA_ACC_HIST_U64: dist.ReduceOp.SUM,  # PERCENTILE value histogram bins (DoubleArrayList.addAll)
+    L.PA_ACC_LANE_COUNT_U64: dist.ReduceOp.SUM,  # filtered aggregations: docs of every lane in every group
     L.PA_ACC_KEYS_I64: None,  # not element-wise reducible (hashed key spaces)
 }
 SECTION_DTYPE = {
@@ -39,6 +40,7 @@ SECTION_DTYPE = {
     L.PA_ACC_DOCS_U64: torch.int64,
     L.PA_ACC_PRESENCE_U8: torch.uint8,
     L.PA_ACC_HIST_U64: torch.int64,
+    L.PA_ACC_LANE_COUNT_U64: torch.int64,
     L.PA_ACC_KEYS_I64: torch.int64,
 }
 # identity of each per-key section (what pa_query_reset leaves in an empty slot)
@@ -531,8 +533,14 @@ class DistributedAccumulators:
         reduce takes it, also under a subgroup). numDocsScanned is summed too, so the merged results block's execution
         statistics are every rank's own pair summed before the collective (one extra 16-byte all-reduce and a host sync
         per query). execution_stats=False skips that (the timed bench steps, which fetch without statistics): the merged
-        block then has no statistics, and a fetch that asks for them raises instead of returning (0, 0)."""
+        block then has no statistics, and a fetch that asks for them raises instead of returning (0, 0).
+        A query with filtered aggregations (AGG(x) FILTER (WHERE ...)) reduces with execution_stats=False only: its
+        statistics are sums over every segment's own swim lanes (engine.GpuQueryExecutor.filtered_stats), which the
+        merged block cannot carry; execution_stats=True raises."""
         ex = self.executor
+        if execution_stats and getattr(ex, "lane_filters", None):
+            raise L.PinotAmdError("a query with aggregation filters has no merged execution statistics: "
+                                  "reduce(execution_stats=False) and fetch(execution_stats=False)")
         if execution_stats:
             local = torch.tensor(list(ex.execution_stats()), dtype=torch.int64, device=self.buf.device)
             if dist.is_initialized():

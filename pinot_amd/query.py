@@ -1,8 +1,9 @@
 """Query model for the hot path (mirror of pinot-core's QueryContext / FilterContext / predicates) and a
 parser for the SQL subset the reference's query tests use on this path:
 
-  SELECT agg(col) [AS alias], ... FROM t [WHERE filter] [GROUP BY c1, ...] [ORDER BY x [ASC|DESC], ...]
-  [LIMIT n] [OPTION(k=v, ...)]
+  SELECT agg(col) [FILTER (WHERE filter)] [AS alias], ... FROM t [WHERE filter] [GROUP BY c1, ...]
+  [ORDER BY x [ASC|DESC], ...] [LIMIT n] [OPTION(k=v, ...)]
+  (agg(col) FILTER (WHERE f): the aggregation over the docs matching WHERE AND f; Aggregation.filter)
   SELECT col, ... | * FROM t [WHERE filter] [ORDER BY c1 [ASC|DESC], ...] [LIMIT [offset,] n | LIMIT n OFFSET m]
   (a selection: Query.is_selection; SelectionOnlyOperator / SelectionOrderByOperator on the server)
   SELECT DISTINCT c1, c2, ... | DISTINCT(c) FROM t [WHERE filter] [ORDER BY ci [ASC|DESC], ...] [LIMIT n]
@@ -18,7 +19,7 @@ forms; PERCENTILE<digits>(col), PERCENTILE<digits>MV(col), PERCENTILE(col, p), P
 """
 import decimal
 import re
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace as dataclasses_replace
 from typing import List, Optional, Tuple
 
 DEFAULT_HLL_LOG2M = 8          # CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M
@@ -180,6 +181,52 @@ def java_double_string(x):
     return "%s%s.%sE%d" % ("-" if sign else "", digits[0], digits[1:] or "0", exp10)
 
 
+def filter_string(f):
+    """FilterContext.toString (FilterContext.java:136-167) over the predicates' toString: EqPredicate.java:64
+    `c = 'v'`, NotEqPredicate.java:63 `c != 'v'`, InPredicate.java:58 / NotInPredicate.java:58 `c IN ('a','b')`,
+    RangePredicate.java:130-142, RegexpLikePredicate.java:72; AND / OR in parentheses, `(NOT x)`, constants true /
+    false. Values print as the query spelled them. Pinned by FilteredAggregationsTest.java:219 and :226."""
+    if isinstance(f, (And, Or)):
+        return "(" + (" AND " if isinstance(f, And) else " OR ").join(filter_string(c) for c in f.children) + ")"
+    if isinstance(f, Not):
+        return "(NOT %s)" % filter_string(f.child)
+    if isinstance(f, BoolFilter):
+        return "true" if f.value else "false"
+    if isinstance(f, EqPredicate):
+        return "%s = '%s'" % (f.column, f.value)
+    if isinstance(f, NotEqPredicate):
+        return "%s != '%s'" % (f.column, f.value)
+    if isinstance(f, (InPredicate, NotInPredicate)):
+        return "%s %s (%s)" % (f.column, "IN" if isinstance(f, InPredicate) else "NOT IN",
+                               ",".join("'%s'" % v for v in f.values))
+    if isinstance(f, RangePredicate):
+        if f.lower == UNBOUNDED:
+            return "%s %s '%s'" % (f.column, "<=" if f.upper_inclusive else "<", f.upper)
+        if f.upper == UNBOUNDED:
+            return "%s %s '%s'" % (f.column, ">=" if f.lower_inclusive else ">", f.lower)
+        if f.lower_inclusive and f.upper_inclusive:
+            return "%s BETWEEN '%s' AND '%s'" % (f.column, f.lower, f.upper)
+        return "(%s %s '%s' AND %s %s '%s')" % (f.column, ">=" if f.lower_inclusive else ">", f.lower,
+                                                f.column, "<=" if f.upper_inclusive else "<", f.upper)
+    if isinstance(f, RegexpLikePredicate):
+        return "regexp_like(%s,'%s')" % (f.column, f.pattern)
+    raise ValueError("no FilterContext string for %r" % (f,))
+
+
+def filter_columns(f, into):
+    """Adds the columns a filter tree reads to the set or list `into`."""
+    if f is None:
+        return into
+    for c in getattr(f, "children", ()) or ():
+        filter_columns(c, into)
+    if getattr(f, "child", None) is not None:
+        filter_columns(f.child, into)
+    col = getattr(f, "column", None)
+    if col is not None and col not in into:
+        into.add(col) if isinstance(into, set) else into.append(col)
+    return into
+
+
 def base_function(fn):
     """Merge/extract semantics of a function: the *MV forms behave like their single-value form, COUNTMV like COUNT."""
     return fn[:-2] if fn.endswith("MV") else fn
@@ -192,9 +239,19 @@ class Aggregation:
     log2m: int = DEFAULT_HLL_LOG2M
     percentile: float = -1.0   # PERCENTILE / PERCENTILEMV: 0..100
     version: int = 0           # PERCENTILE spelling: 0 = PERCENTILE<digits>(col), 1 = PERCENTILE(col, p)
+    filter: object = None      # AGG(col) FILTER (WHERE filter): the filter tree, as written (no optimizer rewrite)
 
     @property
     def result_name(self):
+        """AggregationFunctionUtils.getResultColumnName (:412-418): the function's name, plus
+        " FILTER(WHERE " + FilterContext.toString + ")" for a filtered aggregation."""
+        if self.filter is not None:
+            return "%s FILTER(WHERE %s)" % (dataclasses_replace(self, filter=None).result_name,
+                                            filter_string(self.filter))
+        return self.function_name
+
+    @property
+    def function_name(self):
         """AggregationFunction.getResultColumnName: lower-case function name + (column)."""
         if self.function == "COUNT":
             return "count(*)"
@@ -253,6 +310,7 @@ class Query:
         for a in self.aggregations:
             if a.column:
                 cols.add(a.column)
+            filter_columns(a.filter, cols)
         if self.is_selection or self.is_distinct:
             cols.update(self.select_columns)
             cols.update(o.expr for o in self.order_by if isinstance(o.expr, str))
@@ -344,6 +402,24 @@ class _Parser:
 
     # SELECT list item
     def aggregation(self):
+        """One aggregation call, with its FILTER ( WHERE filter ) clause when one follows the closing parenthesis
+        (every function form; the existing filter grammar)."""
+        agg = self.aggregation_call()
+        tok, nxt = self.peek(), self.peek(1)
+        if tok[0] == "id" and tok[1].upper() == "FILTER":
+            if nxt != ("op", "("):
+                raise ValueError("FILTER clause: expected ( WHERE filter ) after FILTER, at token %r" % (nxt,))
+            self.i += 2
+            try:
+                self.expect_kw("WHERE")
+                f = self.filter_or()
+                self.expect_op(")")
+            except ValueError as e:
+                raise ValueError("FILTER clause: %s" % e) from None
+            agg = dataclasses_replace(agg, filter=f)
+        return agg
+
+    def aggregation_call(self):
         fn = self.ident().upper()
         self.expect_op("(")
         if self.kw("DISTINCT"):
@@ -486,6 +562,8 @@ class _Parser:
                 star = True
             elif tok[0] == "id" and not (nxt[0] == "op" and nxt[1] == "("):
                 plain_cols.append(self.ident())  # group-by column in the select list
+                if self.peek()[0] == "id" and self.peek()[1].upper() == "FILTER":
+                    raise ValueError("FILTER clause: it follows an aggregation, not the column %r" % plain_cols[-1])
             else:
                 aggs.append(self.aggregation())
                 aliases.append(self.ident() if self.kw("AS") else None)
@@ -602,4 +680,6 @@ def query_columns(query):
             (list(query.select_columns) if query.is_distinct else []):
         if n not in names:
             names.append(n)
+    for a in query.aggregations:
+        filter_columns(a.filter, names)
     return names

@@ -77,15 +77,22 @@ def final_value(fn, v):
     return v
 
 
+def _add_stat(a, b):
+    return None if a is None or b is None else a + b
+
+
 def merge_intermediate(results):
     results = list(results)
     out = IntermediateResult(results[0].aggregations, results[0].group_by)
     fns = [a.function for a in out.aggregations]
     for r in results:
-        out.num_docs_scanned += r.num_docs_scanned
+        # (a statistic a server cannot define — numEntriesScannedInFilter of a query with filtered aggregations —
+        # is None, and stays None in the sum)
+        out.num_docs_scanned = _add_stat(out.num_docs_scanned, r.num_docs_scanned)
         out.num_total_docs += r.num_total_docs
-        out.num_entries_scanned_in_filter += r.num_entries_scanned_in_filter
-        out.num_entries_scanned_post_filter += r.num_entries_scanned_post_filter
+        out.num_entries_scanned_in_filter = _add_stat(out.num_entries_scanned_in_filter, r.num_entries_scanned_in_filter)
+        out.num_entries_scanned_post_filter = _add_stat(out.num_entries_scanned_post_filter,
+                                                        r.num_entries_scanned_post_filter)
         out.num_groups_limit_reached |= r.num_groups_limit_reached
         if out.group_by:
             for k, vals in r.groups.items():
