@@ -79,6 +79,10 @@ extern "C" {
 #define PA_MAX_SELECT_COLUMNS 64  /* output columns of a selection */
 #define PA_MAX_SELECT_ROWS 65536  /* rows a selection keeps (offset + limit) */
 #define PA_MAX_AGG_FILTERS 8      /* distinct aggregation filters (AGG(x) FILTER (WHERE ...)) of one query */
+#define PA_MAX_EXPRS 8            /* transform expressions (programs) of one query */
+#define PA_MAX_EXPR_OPS 16        /* three-address operations of one expression program */
+#define PA_MAX_EXPR_REGS 8        /* value registers of an expression program */
+#define PA_MAX_EXPR_COLUMNS 8     /* distinct operand columns of all expressions of one query */
 
 /* error codes */
 #define PA_OK 0
@@ -425,6 +429,95 @@ int pa_query_fetch_lane_counts(pa_query* q, void* stream, int64_t num_groups, in
  * FilteredGroupByOperator.java:159-161), with each segment's own lane structure. After a pa_query_fetch of that scan it
  * returns the counters that fetch read with its own copy (no synchronisation); else it synchronises the device. */
 int pa_query_lane_docs(pa_query* q, int64_t* out);
+
+/* ---------------------------------------------------------------- transform expressions
+ * SUM(ADD(a, b)), AVG(SUB(a, b)), GROUP BY timeConvert(ts, 'MILLISECONDS', 'DAYS'), ...: the TransformOperator the
+ * reference's AggregationPlanNode / GroupByPlanNode put between projection and executor (operator/transform/function/
+ * AdditionTransformFunction, SubtractionTransformFunction, MultiplicationTransformFunction, DivisionTransformFunction,
+ * ModuloTransformFunction, SingleParamMathTransformFunction (abs / ceil / floor), TimeConversionTransformFunction), whose
+ * block values the aggregation functions and NoDictionary{Single,Multi}ColumnGroupKeyGenerator read. Here every
+ * expression is a short three-address program the scan runs per matching doc, after one gather of the operand columns.
+ *
+ * An operation is dst = op(a, b) over PA_MAX_EXPR_REGS value registers, each holding a double (D) or an int64 (L).
+ * An operand is a register (PA_EXPR_ARG_REG, a = its index), an immediate double (PA_EXPR_ARG_F64, imm = its bits) or an
+ * immediate int64 (PA_EXPR_ARG_I64, imm = the value); LOAD_COL alone names a column (PA_EXPR_ARG_COL, a = index into
+ * pa_expr_spec.columns) and takes the conversion in b (PA_EXPR_DOUBLE / PA_EXPR_LONG: the reference's
+ * transformToDoubleValuesSV / transformToLongValuesSV of an INT / LONG / FLOAT / DOUBLE column, dictionary-encoded or
+ * raw: (double)value resp. the Java (long) cast).
+ *   LOAD_COL            D or L
+ *   ADD SUB MUL DIV MOD D x D -> D  (IEEE double; MOD is Java's % = C fmod; a register or a double immediate each)
+ *   ABS CEIL FLOOR      D -> D
+ *   D2L                 D -> L      (Java (long): NaN -> 0, saturating)
+ *   L2D                 L -> D
+ *   TCONV_DIV           L / imm     (b: int64 immediate > 0; truncating toward zero: TimeUnit.convert to a coarser unit)
+ *   TCONV_MUL           L * imm     (b: int64 immediate > 0; saturating at Long.MIN_VALUE / MAX_VALUE: to a finer unit)
+ * The program's value is the register its last operation wrote; its type must be result_type.
+ *
+ * An aggregation (SUM / MIN / MAX only) with agg_expr[i] >= 0 aggregates that program's value in place of a column: a
+ * double value as a DOUBLE column's (PA_ACC_SUM_F64; MIN / MAX in the ordered encoding), an int64 value as a LONG
+ * column's (the exact PA_ACC_SUM_I64X2 pair). A group-by position with group_by_expr[j] >= 0 groups by the value's 64
+ * bits (every NaN made 0x7ff8000000000000 first; -0.0 and 0.0 stay distinct: Double.doubleToLongBits, the hash the
+ * reference's Double2IntOpenHashMap uses) exactly as a raw LONG / DOUBLE column's component: the key space is hashed,
+ * pa_query_key_layout reports the component's shift, and group_by_cardinality[j] is ignored. The spec's column_id at
+ * those positions is ignored.
+ *
+ * A query with expressions runs one of two strategies of its own (workgroup-private LDS accumulators over a direct key
+ * space, or device-scope atomics). pa_query_prepare fails with PA_EUNSUPPORTED when numGroupsLimit trimming would run,
+ * for multi-value, STRING or BYTES operand columns, and next to aggregation filters. */
+#define PA_EXPR_DOUBLE 0
+#define PA_EXPR_LONG 1
+
+#define PA_EXPR_ARG_REG 0
+#define PA_EXPR_ARG_COL 1
+#define PA_EXPR_ARG_F64 2
+#define PA_EXPR_ARG_I64 3
+
+#define PA_EXPR_LOAD_COL 0
+#define PA_EXPR_ADD 1
+#define PA_EXPR_SUB 2
+#define PA_EXPR_MUL 3
+#define PA_EXPR_DIV 4
+#define PA_EXPR_MOD 5
+#define PA_EXPR_ABS 6
+#define PA_EXPR_CEIL 7
+#define PA_EXPR_FLOOR 8
+#define PA_EXPR_D2L 9
+#define PA_EXPR_L2D 10
+#define PA_EXPR_TCONV_DIV 11
+#define PA_EXPR_TCONV_MUL 12
+
+typedef struct {
+  int32_t op;     /* PA_EXPR_* opcode */
+  int32_t dst;    /* 0..PA_MAX_EXPR_REGS-1 */
+  int32_t a_kind; /* PA_EXPR_ARG_* */
+  int32_t a;      /* register / column index */
+  int32_t b_kind;
+  int32_t b;      /* register index; LOAD_COL: PA_EXPR_DOUBLE / PA_EXPR_LONG */
+  int64_t a_imm;  /* immediate: the double's bits, or the int64 */
+  int64_t b_imm;
+} pa_expr_op;
+
+typedef struct {
+  int32_t result_type; /* PA_EXPR_DOUBLE / PA_EXPR_LONG */
+  int32_t num_ops;     /* 1..PA_MAX_EXPR_OPS */
+  pa_expr_op ops[PA_MAX_EXPR_OPS];
+} pa_expr_program;
+
+typedef struct {
+  int32_t num_exprs;   /* 1..PA_MAX_EXPRS */
+  int32_t num_columns; /* 1..PA_MAX_EXPR_COLUMNS */
+  int32_t columns[PA_MAX_EXPR_COLUMNS];     /* column ids of the distinct operand columns */
+  int32_t agg_expr[PA_MAX_AGGS];            /* per spec.aggs[i]: its expression, or -1 */
+  int32_t group_by_expr[PA_MAX_GROUP_BY];   /* per group-by position: its expression, or -1 */
+  pa_expr_program exprs[PA_MAX_EXPRS];
+} pa_expr_spec;
+
+/* Between pa_query_create and the first pa_query_bind_segment (a bind reads the spec's columns, which this call
+ * replaces at the expressions' positions). PA_EINVAL: a call after a bind, counts out of range, an index outside its table, a register
+ * read before it was written, an operand of the wrong type, an expression no aggregation or group-by position uses or
+ * that reads no column, an expression under an aggregation other than SUM / MIN / MAX, a selection or distinct query;
+ * PA_EUNSUPPORTED: a query with aggregation filters. */
+int pa_query_set_expressions(pa_query* q, const pa_expr_spec* spec);
 
 /* Tests and measurement only: overrides one planner decision of this query (the tunings, their ranges and defaults:
  * pinot_amd/csrc/pa_tuning.h; the library reads none of them from the environment). Before pa_query_prepare.

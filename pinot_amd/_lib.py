@@ -16,6 +16,11 @@ PA_MAX_ORDER_BY = 8
 PA_MAX_SELECT_COLUMNS = 64
 PA_MAX_SELECT_ROWS = 65536
 PA_MAX_AGG_FILTERS = 8
+PA_MAX_EXPRS, PA_MAX_EXPR_OPS, PA_MAX_EXPR_REGS, PA_MAX_EXPR_COLUMNS = 8, 16, 8, 8
+PA_EXPR_DOUBLE, PA_EXPR_LONG = 0, 1
+PA_EXPR_ARG_REG, PA_EXPR_ARG_COL, PA_EXPR_ARG_F64, PA_EXPR_ARG_I64 = range(4)
+PA_EXPR_LOAD_COL, PA_EXPR_ADD, PA_EXPR_SUB, PA_EXPR_MUL, PA_EXPR_DIV, PA_EXPR_MOD, PA_EXPR_ABS, PA_EXPR_CEIL, \
+    PA_EXPR_FLOOR, PA_EXPR_D2L, PA_EXPR_L2D, PA_EXPR_TCONV_DIV, PA_EXPR_TCONV_MUL = range(13)
 
 PA_OK, PA_EINVAL, PA_EHIP, PA_ENOMEM, PA_EUNSUPPORTED = 0, -1, -2, -3, -4
 PA_INT, PA_LONG, PA_FLOAT, PA_DOUBLE, PA_STRING, PA_BYTES = range(6)
@@ -71,6 +76,7 @@ EXPORTED = [
     "pa_query_selection_segment_docs", "pa_query_selection_counters",
     "pa_query_set_distinct", "pa_query_fetch_distinct",
     "pa_query_set_agg_filters", "pa_query_fetch_lane_counts", "pa_query_lane_docs",
+    "pa_query_set_expressions",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
     "pa_query_partition_keys",
@@ -149,6 +155,27 @@ class AggFilterSpec(ctypes.Structure):
     ]
 
 
+class ExprOp(ctypes.Structure):
+    _fields_ = [
+        ("op", ctypes.c_int32), ("dst", ctypes.c_int32), ("a_kind", ctypes.c_int32), ("a", ctypes.c_int32),
+        ("b_kind", ctypes.c_int32), ("b", ctypes.c_int32), ("a_imm", ctypes.c_int64), ("b_imm", ctypes.c_int64),
+    ]
+
+
+class ExprProgram(ctypes.Structure):
+    _fields_ = [("result_type", ctypes.c_int32), ("num_ops", ctypes.c_int32), ("ops", ExprOp * PA_MAX_EXPR_OPS)]
+
+
+class ExprSpec(ctypes.Structure):
+    _fields_ = [
+        ("num_exprs", ctypes.c_int32), ("num_columns", ctypes.c_int32),
+        ("columns", ctypes.c_int32 * PA_MAX_EXPR_COLUMNS),
+        ("agg_expr", ctypes.c_int32 * PA_MAX_AGGS),
+        ("group_by_expr", ctypes.c_int32 * PA_MAX_GROUP_BY),
+        ("exprs", ExprProgram * PA_MAX_EXPRS),
+    ]
+
+
 class LeafParams(ctypes.Structure):
     _fields_ = [
         ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("negate", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -193,6 +220,7 @@ def _declare(lib):
         "pa_query_set_agg_filters": (ctypes.c_int, [vp, ctypes.POINTER(AggFilterSpec)]),
         "pa_query_fetch_lane_counts": (ctypes.c_int, [vp, vp, i64, vp]),
         "pa_query_lane_docs": (ctypes.c_int, [vp, vp]),
+        "pa_query_set_expressions": (ctypes.c_int, [vp, ctypes.POINTER(ExprSpec)]),
         "pa_query_prepare": (ctypes.c_int, [vp]),
         "pa_query_num_keys": (i64, [vp]),
         "pa_query_execute": (ctypes.c_int, [vp, vp]),

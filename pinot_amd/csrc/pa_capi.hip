@@ -48,6 +48,7 @@ int pa_query_set_agg_filters(pa_query* q, const pa_agg_filter_spec* spec) {
   for (const pa_segment* seg : q->segs)
     if (seg) return fail(PA_EINVAL, "set the aggregation filters before binding segments");
   if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "aggregation filters on a selection or distinct query");
+  if (q->is_expr) return fail(PA_EUNSUPPORTED, "aggregation filters next to expressions are not supported");
   const pa_query_spec& s = q->spec;
   if (spec->num_filters < 1 || spec->num_filters > PA_MAX_AGG_FILTERS)
     return fail(PA_EINVAL, "aggregation filters: 1.." + std::to_string(PA_MAX_AGG_FILTERS) + " filters");
@@ -78,6 +79,35 @@ int pa_query_set_agg_filters(pa_query* q, const pa_agg_filter_spec* spec) {
   q->filt_lits = lits;
   q->filt_clause_end = ends;
   q->is_filtered = true;
+  return PA_OK;
+}
+
+int pa_query_set_expressions(pa_query* q, const pa_expr_spec* spec) {
+  if (!q || !spec) return fail(PA_EINVAL, "null query or expression spec");
+  if (q->prepared) return fail(PA_EINVAL, "query already prepared");
+  // (the spec's columns at the expressions' positions are rewritten below, and a bind reads them)
+  for (const pa_segment* seg : q->segs)
+    if (seg) return fail(PA_EINVAL, "set the expressions before binding segments");
+  if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "expressions on a selection or distinct query");
+  if (q->is_filtered) return fail(PA_EUNSUPPORTED, "expressions next to aggregation filters are not supported");
+  if (int rc = expr_check_spec(q->spec, *spec)) return rc;
+  q->expr_spec = *spec;
+  q->is_expr = true;
+  // The spec's column at an expression's position is ignored: it becomes the program's first operand column, so every
+  // per-column step of the planner sees a column the query really reads.
+  auto first_col = [&](int e) {
+    const pa_expr_program& p = spec->exprs[e];
+    for (int o = 0; o < p.num_ops; ++o)
+      if (p.ops[o].op == PA_EXPR_LOAD_COL) return spec->columns[p.ops[o].a];
+    return spec->columns[0];
+  };
+  for (int a = 0; a < q->spec.num_aggs; ++a)
+    if (spec->agg_expr[a] >= 0) q->spec.aggs[a].column_id = first_col(spec->agg_expr[a]);
+  for (int j = 0; j < q->spec.num_group_by; ++j)
+    if (spec->group_by_expr[j] >= 0) {
+      q->spec.group_by_columns[j] = first_col(spec->group_by_expr[j]);
+      q->spec.group_by_cardinality[j] = 0;
+    }
   return PA_OK;
 }
 
@@ -174,9 +204,10 @@ int pa_query_prepare(pa_query* q) {
   if (!rc) rc = plan_key_space(q, P);
   if (!rc) rc = plan_limit(q, P);
   // (a distinct query and a query with aggregation filters have their own two strategies each)
-  if (!rc && !q->is_distinct && !q->is_filtered) rc = plan_gdense(q, P);
+  if (!rc && !q->is_distinct && !q->is_filtered && !q->is_expr) rc = plan_gdense(q, P);
   if (!rc) rc = build_segments(q, P);
   if (!rc && q->is_filtered) rc = filtered_validate(q, P);
+  if (!rc && q->is_expr) rc = expr_validate(q, P);
   if (!rc) rc = plan_walk(q, P);
   if (!rc) rc = plan_accumulators(q, P);
   TilePlan plan, count_plan;
@@ -201,6 +232,10 @@ int pa_query_prepare(pa_query* q) {
   fill_devquery(q, P, plan, total_tiles);
   if (q->is_filtered) {
     rc = filtered_plan(q, P);
+    if (rc) return rc;
+  }
+  if (q->is_expr) {
+    rc = expr_plan(q, P);
     if (rc) return rc;
   }
   rc = plan_leaps(q, P);

@@ -63,12 +63,19 @@ enum Strategy : int32_t {
   // filtered aggregations (AGG(x) FILTER (WHERE ...)): filter + one mask per aggregation filter ("lane") over the
   // surviving docs + per-lane aggregation (pa_scan.h "filtered aggregations"): workgroup-private accumulators in LDS,
   // flushed once per workgroup, or device-scope atomics
-  STRAT_FILTERED_LDS = 131, STRAT_FILTERED = 132
+  STRAT_FILTERED_LDS = 131, STRAT_FILTERED = 132,
+  // transform expressions (SUM(ADD(a, b)), GROUP BY timeConvert(...)): filter + one gather of the operand columns + the
+  // expression programs per matching doc (pa_scan.h "expressions"): workgroup-private accumulators in LDS over a direct
+  // key space, flushed once per workgroup, or device-scope atomics (direct or hashed key space)
+  STRAT_EXPR_LDS = 133, STRAT_EXPR = 134
 };
 __host__ __device__ constexpr bool is_distinct(int s) { return s == STRAT_DISTINCT_LDS || s == STRAT_DISTINCT; }
 __host__ __device__ constexpr bool is_filtered(int s) { return s == STRAT_FILTERED_LDS || s == STRAT_FILTERED; }
 // strategies whose accumulators (Acc<STRAT>) are the workgroup's LDS copies
-__host__ __device__ constexpr bool acc_in_lds(int s) { return s == STRAT_LDS || s == STRAT_FILTERED_LDS; }
+__host__ __device__ constexpr bool is_expr(int s) { return s == STRAT_EXPR_LDS || s == STRAT_EXPR; }
+__host__ __device__ constexpr bool acc_in_lds(int s) {
+  return s == STRAT_LDS || s == STRAT_FILTERED_LDS || s == STRAT_EXPR_LDS;
+}
 __host__ __device__ constexpr bool is_pcount(int s) { return s == STRAT_PCOUNT || s == STRAT_PCOUNT_MV; }
 // STRAT_GDENSE: 4-wave workgroups; STRAT_GDENSE8 / STRAT_GDENSE12: the same kernel with 8- / 12-wave workgroups (2 / 3
 // waves per SIMD when one workgroup fits a CU, e.g. beside a 64 KiB value table: the walk's LDS round trips and VALU
@@ -339,6 +346,29 @@ struct DevQuery {
   const struct SelDesc* sel;     // STRAT_SELECT: the selection's descriptor (nullptr otherwise)
   uint32_t* keybits;             // distinct: the key-presence bitmap (PA_ACC_KEYBITS_U32), (num_keys + 31) / 32 words
   const struct FiltDesc* filt;   // filtered aggregations: the lanes' descriptor (nullptr otherwise)
+  const struct ExprDesc* expr;   // transform expressions: the programs' descriptor (nullptr otherwise)
+};
+// ---------------------------------------------------------------- transform expressions (STRAT_EXPR_LDS / STRAT_EXPR)
+// The validated programs of pa_query_set_expressions (pinot_amd.h "transform expressions"), wave-uniform: the scan reads
+// them through the constant address space, so the opcode dispatch is scalar control flow.
+struct ExprOp {
+  int32_t op, dst;       // PA_EXPR_*, destination register
+  int32_t a_kind, a;     // PA_EXPR_ARG_*: register / operand-column index
+  int32_t b_kind, b;     // LOAD_COL: b = PA_EXPR_DOUBLE / PA_EXPR_LONG
+  int64_t a_imm, b_imm;  // immediates (a double's bits, or an int64)
+};
+struct ExprProg {
+  int32_t result_type;   // PA_EXPR_DOUBLE / PA_EXPR_LONG
+  int32_t num_ops;
+  ExprOp ops[PA_MAX_EXPR_OPS];
+};
+struct ExprDesc {
+  int32_t num_exprs;
+  int32_t num_cols;
+  int32_t col_slot[PA_MAX_EXPR_COLUMNS];  // operand column c -> column slot (DevSeg::cols)
+  int32_t agg_expr[PA_MAX_AGGS];          // aggregation a's program, or -1
+  int32_t gb_expr[PA_MAX_GROUP_BY];       // group-by position j's program, or -1
+  ExprProg progs[PA_MAX_EXPRS];
 };
 // ---------------------------------------------------------------- filtered aggregations (STRAT_FILTERED_LDS / STRAT_FILTERED)
 // AGG(x) FILTER (WHERE F): aggregations with an equal filter share a lane (AggregationFunctionUtils.java:340-373), the

@@ -346,8 +346,15 @@ struct pa_query {
   DevBuf filt_desc, filt_leaves, filt_seg_docs, lane_buf;
   int lane_section = -1;
   std::vector<int64_t> filt_seg_docs_host;  // filt_seg_docs as the last fetch read it ([nseg][num_filters + 1])
+  // transform expressions (pa_query_set_expressions; pa_scan.h "expressions"): the validated spec, and the descriptor
+  // the scan reads with its device copy
+  bool is_expr = false;
+  pa_expr_spec expr_spec{};
+  ExprDesc hexpr{};
+  DevBuf expr_desc;
 
   ~pa_query() {
+    dev_free(expr_desc);
     dev_free(filt_desc);
     dev_free(filt_leaves);
     dev_free(filt_seg_docs);
@@ -419,6 +426,7 @@ struct Prep {
   size_t lds_acc = 0;  // LDS strategy: accumulator bytes
   std::vector<size_t> agg_lds;
   size_t lane_count_lds = 0;  // filtered aggregations, LDS variant: byte offset of the workgroup's lane counts
+  std::vector<int> expr_slot;  // transform expressions: the column slot of every operand column
   bool filt_dense = true;     // filtered aggregations: the lanes' union is expected to keep a doc per wave tile or more
   // STRAT_GDENSE (plan_gdense)
   bool gdense = false;
@@ -458,6 +466,9 @@ int upload_owned(pa_query* q, const void* host, size_t bytes, void** dev);
 int to_cnf_program(const int32_t* ops, int num_ops, int num_leaves, std::vector<Clause>& out);
 int filtered_validate(pa_query* q, Prep& P);        // prepare, after build_segments: what a filtered query refuses
 int filtered_plan(pa_query* q, const Prep& P);      // prepare, after fill_devquery: the lanes' descriptor, uploaded
+int expr_check_spec(const pa_query_spec& s, const pa_expr_spec& e);  // pa_query_set_expressions: the programs' validation
+int expr_validate(pa_query* q, Prep& P);            // prepare, after build_segments: what an expression query refuses
+int expr_plan(pa_query* q, const Prep& P);          // prepare, after fill_devquery: the programs' descriptor, uploaded
 int mv_group_component(const pa_query* q);
 int plan_filter(pa_query* q, Prep& P);
 int plan_slots(pa_query* q, Prep& P);

@@ -227,6 +227,15 @@ int plan_slots(pa_query* q, Prep& P) {
   // (the aggregation filters run on the docs the query's own filter kept: their columns are post-filter columns)
   for (const std::vector<Literal>& lits : q->filt_lits)
     for (const Literal& lit : lits) P.slot_post[P.leaf_slot[lit.leaf]] = 1;
+  // (so are the operand columns of the expressions, which the matching docs' gather reads)
+  P.expr_slot.clear();
+  if (q->is_expr)
+    for (int c = 0; c < q->expr_spec.num_columns; ++c) {
+      const int sl = slot_of(q, q->expr_spec.columns[c]);
+      if (sl < 0) return fail(PA_EUNSUPPORTED, "too many distinct columns in one query");
+      P.expr_slot.push_back(sl);
+      P.slot_post[sl] = 1;
+    }
   int post_bits = 0;
   for (int sl = 0; sl < kMaxSlots; ++sl) {
     if (!P.slot_post[sl] || sl >= (int)q->slot_cols.size() || !q->nseg) continue;
@@ -262,6 +271,13 @@ int plan_key_space(pa_query* q, Prep& P) {
   int64_t K = 1;
   P.stride.assign(s.num_group_by, 0);
   for (int j = 0; j < s.num_group_by; ++j) {
+    if (q->is_expr && q->expr_spec.group_by_expr[j] >= 0) {
+      // an expression's component is its 64 result bits, packed like a raw LONG / DOUBLE column's value
+      P.gb_raw[j] = 1;
+      gb_bits[j] = 64;
+      direct_ok = false;
+      continue;
+    }
     auto it = q->segs[0]->cols.find(s.group_by_columns[j]);
     if (it == q->segs[0]->cols.end()) return fail(PA_EINVAL, "group-by column missing in segment 0");
     if (it->second->kind == COL_SV_RAW) {
@@ -308,7 +324,8 @@ int plan_key_space(pa_query* q, Prep& P) {
     }
     if (s.hash_keys_bound > 0) bound = std::max<uint64_t>(bound, (uint64_t)s.hash_keys_bound);
     uint64_t H = 1024;
-    while (H < 2 * bound && H < kMaxHashSlots) H <<= 1;
+    const uint64_t cap = q->tune.hash_slots_cap > 0 ? (uint64_t)q->tune.hash_slots_cap : kMaxHashSlots;
+    while (H < 2 * bound && 2 * H <= cap) H <<= 1;
     q->hashed = true;
     q->ht_slots = (int64_t)H;
     K = (int64_t)H + 1;  // + the reserved slot of the key INT64_MAX (the table's empty marker)
@@ -359,6 +376,19 @@ int plan_limit(pa_query* q, Prep& P) {
       auto it = seg->cols.find(s.group_by_columns[j]);
       if (it == seg->cols.end()) return fail(PA_EINVAL, "group-by column missing in segment " + std::to_string(si));
       const Column* c = it->second;
+      if (q->is_expr && q->expr_spec.group_by_expr[j] >= 0) {
+        // an expression's distinct values: at most the docs, and at most the product of its operand dictionaries
+        uint64_t prod = 1;
+        const pa_expr_program& ep = q->expr_spec.exprs[q->expr_spec.group_by_expr[j]];
+        for (int o = 0; o < ep.num_ops; ++o) {
+          if (ep.ops[o].op != PA_EXPR_LOAD_COL) continue;
+          auto oc = seg->cols.find(q->expr_spec.columns[ep.ops[o].a]);
+          const bool dict = oc != seg->cols.end() && oc->second->kind == COL_SV_DICT;
+          prod = sat_mul(prod, dict ? (uint64_t)oc->second->cardinality : (uint64_t)seg->num_docs);
+        }
+        distinct = sat_mul(distinct, std::min<uint64_t>(prod, (uint64_t)seg->num_docs));
+        continue;
+      }
       distinct = sat_mul(distinct, c->kind == COL_SV_RAW ? (uint64_t)seg->num_docs : (uint64_t)c->cardinality);
       if (c->kind == COL_MV_DICT) {
         per_doc = sat_mul(per_doc, (uint64_t)c->max_values);
@@ -895,6 +925,10 @@ int build_segments(pa_query* q, Prep& P) {
     // group-by remaps
     for (int j = 0; j < s.num_group_by; ++j) {
       const DevCol& dc = d.cols[P.gb_slot[j]];
+      if (q->is_expr && q->expr_spec.group_by_expr[j] >= 0) {
+        if (q->has_remap[si][j]) return fail(PA_EINVAL, "a group remap at an expression's group-by position");
+        continue;
+      }
       if (P.gb_raw[j]) {
         if (dc.kind != COL_SV_RAW || dc.vtype != q->segs[0]->cols.at(s.group_by_columns[j])->vtype)
           return fail(PA_EINVAL, "a raw group-by column must be raw with the same type in every segment");
@@ -922,6 +956,12 @@ int build_segments(pa_query* q, Prep& P) {
       const pa_agg_spec& A = s.aggs[a];
       if (A.type == PA_AGG_COUNT) continue;
       const Column* c = seg->cols.at(A.column_id);
+      if (q->is_expr && q->expr_spec.agg_expr[a] >= 0) {
+        // the program's value in place of a column's: a double as a DOUBLE column, an int64 as a LONG column
+        P.agg_src[a] = q->expr_spec.exprs[q->expr_spec.agg_expr[a]].result_type == PA_EXPR_DOUBLE ? SRC_DOUBLE : SRC_LONG;
+        P.val_fast[a] = 0;
+        continue;
+      }
       if (c->kind == COL_MV_DICT) {
         q->has_mv = 1;
         P.agg_mv[a] = 1;
@@ -1063,6 +1103,141 @@ int plan_accumulators(pa_query* q, Prep& P) {
     P.lane_count_lds = P.lds_acc;
     P.lds_acc += ((size_t)q->filt_spec.num_filters * (size_t)K * 4 + 15) & ~(size_t)15;
   }
+  return PA_OK;
+}
+
+// pa_query_set_expressions: the programs against the operation table of pinot_amd.h "transform expressions" (counts,
+// indices, every register written before it is read, operand types, the result type), and their use by the spec.
+int expr_check_spec(const pa_query_spec& s, const pa_expr_spec& e) {
+  if (e.num_exprs < 1 || e.num_exprs > PA_MAX_EXPRS)
+    return fail(PA_EINVAL, "expressions: 1.." + std::to_string(PA_MAX_EXPRS) + " programs");
+  if (e.num_columns < 1 || e.num_columns > PA_MAX_EXPR_COLUMNS)
+    return fail(PA_EINVAL, "expressions: 1.." + std::to_string(PA_MAX_EXPR_COLUMNS) + " operand columns");
+  for (int c = 0; c < e.num_columns; ++c)
+    for (int d = 0; d < c; ++d)
+      if (e.columns[c] == e.columns[d]) return fail(PA_EINVAL, "expressions: an operand column listed twice");
+  std::vector<char> used(e.num_exprs, 0), col_used(e.num_columns, 0);
+  for (int a = 0; a < s.num_aggs; ++a) {
+    const int x = e.agg_expr[a];
+    if (x < -1 || x >= e.num_exprs) return fail(PA_EINVAL, "aggregation expression index out of range");
+    if (x < 0) continue;
+    const int t = s.aggs[a].type;
+    if (t != PA_AGG_SUM && t != PA_AGG_MIN && t != PA_AGG_MAX)
+      return fail(PA_EINVAL, "an expression under an aggregation other than SUM / MIN / MAX");
+    used[x] = 1;
+  }
+  for (int j = 0; j < s.num_group_by; ++j) {
+    const int x = e.group_by_expr[j];
+    if (x < -1 || x >= e.num_exprs) return fail(PA_EINVAL, "group-by expression index out of range");
+    if (x >= 0) used[x] = 1;
+  }
+  for (int x = 0; x < e.num_exprs; ++x) {
+    if (!used[x]) return fail(PA_EINVAL, "an expression no aggregation or group-by position uses");
+    const pa_expr_program& p = e.exprs[x];
+    if (p.result_type != PA_EXPR_DOUBLE && p.result_type != PA_EXPR_LONG) return fail(PA_EINVAL, "expression: bad result type");
+    if (p.num_ops < 1 || p.num_ops > PA_MAX_EXPR_OPS)
+      return fail(PA_EINVAL, "expression: 1.." + std::to_string(PA_MAX_EXPR_OPS) + " operations");
+    int type[PA_MAX_EXPR_REGS];  // -1: not written yet
+    for (int& t : type) t = -1;
+    bool reads_column = false;
+    int last = -1;
+    // operand of `want` type (PA_EXPR_DOUBLE / PA_EXPR_LONG): a written register of that type, or its immediate
+    auto operand = [&](int kind, int idx, int want) {
+      if (kind == PA_EXPR_ARG_REG) return idx >= 0 && idx < PA_MAX_EXPR_REGS && type[idx] == want;
+      return kind == (want == PA_EXPR_DOUBLE ? PA_EXPR_ARG_F64 : PA_EXPR_ARG_I64);
+    };
+    for (int o = 0; o < p.num_ops; ++o) {
+      const pa_expr_op& X = p.ops[o];
+      if (X.dst < 0 || X.dst >= PA_MAX_EXPR_REGS) return fail(PA_EINVAL, "expression: destination register out of range");
+      int out;
+      switch (X.op) {
+        case PA_EXPR_LOAD_COL:
+          if (X.a_kind != PA_EXPR_ARG_COL || X.a < 0 || X.a >= e.num_columns)
+            return fail(PA_EINVAL, "expression: LOAD_COL names no operand column");
+          if (X.b != PA_EXPR_DOUBLE && X.b != PA_EXPR_LONG) return fail(PA_EINVAL, "expression: LOAD_COL conversion");
+          col_used[X.a] = 1;
+          reads_column = true;
+          out = X.b;
+          break;
+        case PA_EXPR_ADD: case PA_EXPR_SUB: case PA_EXPR_MUL: case PA_EXPR_DIV: case PA_EXPR_MOD:
+          if (!operand(X.a_kind, X.a, PA_EXPR_DOUBLE) || !operand(X.b_kind, X.b, PA_EXPR_DOUBLE))
+            return fail(PA_EINVAL, "expression: arithmetic takes double registers (written before) or double immediates");
+          out = PA_EXPR_DOUBLE;
+          break;
+        case PA_EXPR_ABS: case PA_EXPR_CEIL: case PA_EXPR_FLOOR: case PA_EXPR_D2L:
+          if (!operand(X.a_kind, X.a, PA_EXPR_DOUBLE))
+            return fail(PA_EINVAL, "expression: operand is not a double register (written before) or immediate");
+          out = X.op == PA_EXPR_D2L ? PA_EXPR_LONG : PA_EXPR_DOUBLE;
+          break;
+        case PA_EXPR_L2D:
+          if (!operand(X.a_kind, X.a, PA_EXPR_LONG))
+            return fail(PA_EINVAL, "expression: L2D takes a long register (written before) or immediate");
+          out = PA_EXPR_DOUBLE;
+          break;
+        case PA_EXPR_TCONV_DIV: case PA_EXPR_TCONV_MUL:
+          if (!operand(X.a_kind, X.a, PA_EXPR_LONG) || X.b_kind != PA_EXPR_ARG_I64 || X.b_imm <= 0)
+            return fail(PA_EINVAL, "expression: TCONV takes a long operand and a positive int64 immediate");
+          out = PA_EXPR_LONG;
+          break;
+        default: return fail(PA_EINVAL, "expression: unknown opcode");
+      }
+      type[X.dst] = out;
+      last = out;
+    }
+    if (!reads_column) return fail(PA_EINVAL, "an expression that reads no column");
+    if (last != p.result_type) return fail(PA_EINVAL, "expression: the last operation's type is not the result type");
+  }
+  for (int c = 0; c < e.num_columns; ++c)
+    if (!col_used[c]) return fail(PA_EINVAL, "expressions: an operand column no program reads");
+  return PA_OK;
+}
+
+// An expression query against what the scan's evaluator covers (pa_scan.h "expressions").
+int expr_validate(pa_query* q, Prep& P) {
+  const pa_query_spec& s = q->spec;
+  if (q->limit_mode || q->limit_walk)
+    return fail(PA_EUNSUPPORTED, "expressions where numGroupsLimit trimming would run are not supported");
+  if (q->has_mv || P.gb_mv)
+    return fail(PA_EUNSUPPORTED, "a multi-value group-by or aggregation column next to expressions is not supported");
+  for (int a = 0; a < s.num_aggs; ++a)
+    if (s.aggs[a].type == PA_AGG_VALUE_HISTOGRAM || s.aggs[a].type == PA_AGG_COUNT_MV)
+      return fail(PA_EUNSUPPORTED, "VALUE_HISTOGRAM / COUNT_MV next to expressions is not supported");
+  for (int si = 0; si < q->nseg; ++si)
+    for (int c = 0; c < q->expr_spec.num_columns; ++c) {
+      auto it = q->segs[si]->cols.find(q->expr_spec.columns[c]);
+      if (it == q->segs[si]->cols.end()) return fail(PA_EINVAL, "expression operand column missing in a segment");
+      const Column* col = it->second;
+      if (col->kind != COL_SV_DICT && col->kind != COL_SV_RAW)
+        return fail(PA_EUNSUPPORTED, "a multi-value operand column in an expression is not supported");
+      if (col->vtype != PA_INT && col->vtype != PA_LONG && col->vtype != PA_FLOAT && col->vtype != PA_DOUBLE)
+        return fail(PA_EUNSUPPORTED, "a STRING / BYTES operand column in an expression is not supported");
+      if (col->kind == COL_SV_DICT && !col->dict.p) return fail(PA_EINVAL, "dictionary values missing");
+    }
+  return PA_OK;
+}
+
+// The programs' descriptor, uploaded: the validated spec with every operand column's slot.
+int expr_plan(pa_query* q, const Prep& P) {
+  const pa_expr_spec& e = q->expr_spec;
+  ExprDesc& E = q->hexpr;
+  std::memset(&E, 0, sizeof(E));
+  E.num_exprs = e.num_exprs;
+  E.num_cols = e.num_columns;
+  for (int c = 0; c < e.num_columns; ++c) E.col_slot[c] = P.expr_slot[c];
+  for (int a = 0; a < PA_MAX_AGGS; ++a) E.agg_expr[a] = a < q->spec.num_aggs ? e.agg_expr[a] : -1;
+  for (int j = 0; j < PA_MAX_GROUP_BY; ++j) E.gb_expr[j] = j < q->spec.num_group_by ? e.group_by_expr[j] : -1;
+  for (int x = 0; x < e.num_exprs; ++x) {
+    E.progs[x].result_type = e.exprs[x].result_type;
+    E.progs[x].num_ops = e.exprs[x].num_ops;
+    for (int o = 0; o < e.exprs[x].num_ops; ++o) {
+      const pa_expr_op& X = e.exprs[x].ops[o];
+      E.progs[x].ops[o] = ExprOp{X.op, X.dst, X.a_kind, X.a, X.b_kind, X.b, X.a_imm, X.b_imm};
+    }
+  }
+  int rc = dev_alloc(q->expr_desc, sizeof(ExprDesc));
+  if (rc) return rc;
+  PA_HIP(hipMemcpy(q->expr_desc.p, &E, sizeof(E), hipMemcpyHostToDevice));
+  q->hq.expr = (const ExprDesc*)q->expr_desc.p;
   return PA_OK;
 }
 

@@ -514,6 +514,34 @@ int plan_kernels(pa_query* q, Prep& P, TilePlan& plan, TilePlan& count_plan) {
     q->dma_slots = plan.dma;
     return PA_OK;
   }
+  if (q->is_expr) {
+    // Expressions: the step-major scan with the evaluator strategies. Workgroup-private LDS accumulators by STRAT_LDS's
+    // rule — a direct key space whose block takes at most 64 KiB next to the tile ring, and dense matches — else
+    // device-scope atomics (always over a hashed key space). Tuning expr_lds forces either (1: whenever the key space is
+    // direct and the block fits at all).
+    q->partitioned = false;
+    P.lm = false;
+    plan = TilePlan{};
+    const int force = q->tune.expr_lds;
+    const bool want_lds = !q->hashed && (force < 0 ? (!(s.flags & PA_QF_FORCE_GLOBAL) && P.lds_acc <= 64 * 1024 &&
+                                                      (P.dense || (s.flags & PA_QF_FORCE_LDS)))
+                                                   : (force == 1 && P.lds_acc < kLdsBudget));
+    if (want_lds) plan = plan_tiles(q, q->hsegs, STRAT_EXPR_LDS, false, P.lds_acc, false);
+    if (plan.score >= 0) {
+      q->strategy = STRAT_EXPR_LDS;
+    } else {
+      q->strategy = STRAT_EXPR;
+      P.lds_acc = 0;
+      plan = plan_tiles(q, q->hsegs, STRAT_EXPR, false, 0, false);
+    }
+    if (plan.score < 0) return fail(PA_EUNSUPPORTED, "staged columns too wide for the LDS tile ring");
+    PLAN_LOG("expressions: K=%lld programs=%d %s accumulators", (long long)K, q->expr_spec.num_exprs,
+             q->strategy == STRAT_EXPR_LDS ? "LDS" : "global");
+    q->lds_bytes = (int)plan.lds;
+    q->steps = plan.steps;
+    q->dma_slots = plan.dma;
+    return PA_OK;
+  }
   // Lane-major kernel: every eager literal is a dictionary leaf on a staged column and the per-segment plan table
   // has room for the staged columns and eager literals (otherwise the step-major kernel runs the query).
   bool lm = !(s.flags & (PA_QF_NO_LANE_MAJOR | PA_QF_STEPS16)) && q->num_eager <= kLmEager;
@@ -841,7 +869,7 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
   h.lds_count_off = 0;
   h.keybits = q->is_distinct ? (uint32_t*)q->sections[0].ptr : nullptr;
   h.lds_acc_bytes = (q->strategy == STRAT_LDS || is_gdense(q->strategy) || is_lane(q->strategy) || q->strategy == STRAT_SELECT ||
-                     q->strategy == STRAT_DISTINCT_LDS || q->strategy == STRAT_FILTERED_LDS)
+                     q->strategy == STRAT_DISTINCT_LDS || q->strategy == STRAT_FILTERED_LDS || q->strategy == STRAT_EXPR_LDS)
                         ? (uint32_t)P.lds_acc : 0;
   if (is_gdense(q->strategy)) {
     // per-segment parameter tables (GdSegPlan): the query's key box and LDS layout + the segment's staged regions

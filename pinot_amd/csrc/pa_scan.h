@@ -366,12 +366,10 @@ __device__ __forceinline__ int64_t key_slot(const DevQuery* __restrict__ q, int6
 // One aggregation's update for one set of lanes of a 64-doc step (`in`: this lane belongs to the set). grouped: the set
 // shares the key k0, so SUM / MIN / MAX are reduced across the wave and lane `leader` updates once; else every lane of
 // the set updates its own `key`. HLL registers, presence bytes and histogram bins are always per lane.
+// (agg_apply_set: the update with the value already read — a column's by agg_update_set, an expression's by expr_step)
 template <int STRAT>
-__device__ __forceinline__ void agg_update_set(const DevAgg& A, int a, const DevSeg* __restrict__ seg,
-                                               const uint32_t* img, int doc_local, int64_t doc, int64_t key, int64_t k0,
-                                               bool in, bool grouped, int leader, int lane, const Acc<STRAT>& acc) {
-  AggValue v{0, 0.0};
-  if (in) v = agg_value(A, a, seg, img, doc_local, doc);
+__device__ __forceinline__ void agg_apply_set(const DevAgg& A, const AggValue& v, int64_t key, int64_t k0, bool in,
+                                              bool grouped, int leader, int lane, const Acc<STRAT>& acc) {
   if (A.type == PA_AGG_DISTINCTCOUNTHLL) {
     if (in) acc.max_hll(A, key, (uint32_t)v.i);
   } else if (A.type == PA_AGG_DISTINCTCOUNT) {
@@ -422,20 +420,62 @@ __device__ __forceinline__ void agg_update_set(const DevAgg& A, int a, const Dev
   }
 }
 
-// Accumulate the matched lanes (`matched` = wave mask) of one 64-doc step.
+template <int STRAT>
+__device__ __forceinline__ void agg_update_set(const DevAgg& A, int a, const DevSeg* __restrict__ seg,
+                                               const uint32_t* img, int doc_local, int64_t doc, int64_t key, int64_t k0,
+                                               bool in, bool grouped, int leader, int lane, const Acc<STRAT>& acc) {
+  AggValue v{0, 0.0};
+  if (in) v = agg_value(A, a, seg, img, doc_local, doc);
+  agg_apply_set<STRAT>(A, v, key, k0, in, grouped, leader, lane, acc);
+}
+
+// (masks over values, not conditionals between array elements: the compiler turns a chain of conditional element reads
+// back into one indexed load, and the array would then live in scratch memory; cf. filt_pair_mask)
+__device__ __forceinline__ uint64_t expr_get(const uint64_t (&v)[PA_MAX_EXPR_REGS], int i) {
+  uint64_t r = 0;
+#pragma unroll
+  for (int k = 0; k < PA_MAX_EXPR_REGS; ++k) r |= v[k] & (0ull - (uint64_t)(i == k));
+  return r;
+}
+__device__ __forceinline__ void expr_set(uint64_t (&v)[PA_MAX_EXPR_REGS], int i, uint64_t x) {
+#pragma unroll
+  for (int k = 0; k < PA_MAX_EXPR_REGS; ++k) {
+    const uint64_t m = 0ull - (uint64_t)(i == k);
+    v[k] = (x & m) | (v[k] & ~m);
+  }
+}
+// What expr_step hands accumulate_step (pa_scan.h "expressions"): the programs' descriptor and their results for this
+// lane's doc.
+struct ExprVals {
+  const ExprDesc* E;
+  uint64_t res[PA_MAX_EXPRS];
+};
+
+// Accumulate the matched lanes (`matched` = wave mask) of one 64-doc step. The expression strategies pass `ev`: a
+// group-by position or aggregation with a program takes that program's result in place of its column's value.
 template <int STRAT>
 __device__ __forceinline__ void accumulate_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                                 const uint32_t* img, int doc_local, int64_t doc,
-                                                uint64_t matched, int lane, const Acc<STRAT>& acc) {
+                                                uint64_t matched, int lane, const Acc<STRAT>& acc,
+                                                const ExprVals* ev = nullptr) {
   bool mine = (matched >> lane) & 1ull;
   // table-wide group key (DictionaryBasedGroupKeyGenerator: rawKey = sum dictId_j * prod_{k<j} card_k), or the packed
   // key's accumulator slot in the hashed key space
   int64_t key = 0;
   if (mine) {
     int64_t kw[2] = {0, 0};  // (two words: DevQuery::gb_word)
-    for (int j = 0; j < q->num_gb; ++j)
-      kw[q->gb_word[j]] += (int64_t)(gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc) *
-                                     (uint64_t)q->gb_stride[j]);
+    if constexpr (is_expr(STRAT)) {
+      for (int j = 0; j < q->num_gb; ++j) {
+        const int ge = ev->E->gb_expr[j];
+        const uint64_t comp = ge >= 0 ? expr_get(ev->res, ge)
+                                      : gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc);
+        kw[q->gb_word[j]] += (int64_t)(comp * (uint64_t)q->gb_stride[j]);
+      }
+    } else {
+      for (int j = 0; j < q->num_gb; ++j)
+        kw[q->gb_word[j]] += (int64_t)(gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc) *
+                                       (uint64_t)q->gb_stride[j]);
+    }
     key = key_slot(q, kw[0], kw[1]);
     if (key < 0) mine = false;
   }
@@ -463,6 +503,15 @@ __device__ __forceinline__ void accumulate_step(const DevQuery* __restrict__ q, 
     for (int a = 0; a < q->num_aggs; ++a) {
       const DevAgg& A = q->aggs[a];
       if (A.type == PA_AGG_COUNT) continue;
+      if constexpr (is_expr(STRAT)) {
+        const int ae = ev->E->agg_expr[a];
+        if (ae >= 0) {  // the program's value: a double as SRC_DOUBLE, an int64 as SRC_LONG
+          const uint64_t x = expr_get(ev->res, ae);
+          const AggValue v{(int64_t)x, __builtin_bit_cast(double, x)};
+          agg_apply_set<STRAT>(A, v, key, k0, in, grouped, leader, lane, acc);
+          continue;
+        }
+      }
       agg_update_set<STRAT>(A, a, seg, img, doc_local, doc, key, k0, in, grouped, leader, lane, acc);
     }
   }
@@ -3312,6 +3361,158 @@ __device__ __forceinline__ void filtered_lds_flush(const DevQuery* q, unsigned c
   }
 }
 
+// ---------------------------------------------------------------- expressions (STRAT_EXPR_LDS / STRAT_EXPR)
+// SUM(ADD(a, b)), GROUP BY timeConvert(ts, 'MILLISECONDS', 'DAYS'), ...: the reference puts a TransformOperator between
+// projection and executor (AggregationPlanNode / GroupByPlanNode), and the aggregation functions and
+// NoDictionary{Single,Multi}ColumnGroupKeyGenerator read its block values. Here a matching doc of a 64-doc step takes
+// two phases:
+//   gather    every distinct operand column of the query's expressions (ExprDesc::col_slot) is read once: first every
+//             dictionary column's dictId (staged image or HBM) and every raw column's value, then every dictionary
+//             gather — independent loads, issued back to back, so the step pays one HBM latency per phase, not one per
+//             operand. A value is kept as 64 bits in its family: int64 (INT / LONG) or double (FLOAT widened / DOUBLE).
+//   evaluate  the programs (ExprProg) run over eight 64-bit value registers. The program is wave-uniform and read with
+//             scalar loads, so the opcode dispatch is scalar control flow; the lanes differ only in their values.
+// Registers, column values and results are small arrays touched only with compile-time indices (a select chain per
+// access with the uniform runtime index: expr_get / expr_set), so they stay in VGPRs: no scratch memory, whose
+// accesses would wait behind the DMA ring.
+// A DOUBLE result aggregates as SRC_DOUBLE, a LONG result as SRC_LONG (agg_apply_set, the equal-key sets of
+// accumulate_step); a group-by expression contributes its 64 result bits (NaNs made one: doubleToLongBits) as a raw
+// LONG / DOUBLE column does, so such a query's key space is hashed.
+
+// Java's (long) cast of a double: NaN -> 0, saturating.
+__device__ __forceinline__ int64_t java_d2l(double d) {
+  if (d != d) return 0;
+  if (d >= 9223372036854775808.0) return INT64_MAX;
+  if (d <= -9223372036854775808.0) return INT64_MIN;
+  return (int64_t)d;
+}
+
+// TimeUnit.convert to a finer unit: d * m saturating at Long.MIN_VALUE / MAX_VALUE (m > 0).
+__device__ __forceinline__ int64_t tconv_mul(int64_t d, int64_t m) {
+  const int64_t over = INT64_MAX / m;
+  if (d > over) return INT64_MAX;
+  if (d < -over) return INT64_MIN;
+  return d * m;
+}
+
+// (expr_get / expr_set, the mask chains over the eight-element arrays: above accumulate_step, which reads the results)
+static_assert(PA_MAX_EXPR_REGS == PA_MAX_EXPR_COLUMNS && PA_MAX_EXPR_REGS == PA_MAX_EXPRS,
+              "expr_get / expr_set serve the registers, the column values and the results");
+
+// Gather phase: cv[c] = the doc's value of operand column c (int64, or a double's bits); bit c of the returned mask:
+// the column is FLOAT / DOUBLE in this segment (wave-uniform). Lanes outside `in` load nothing and hold zeros.
+__device__ __forceinline__ uint32_t expr_gather(const ExprDesc* __restrict__ E, const DevSeg* __restrict__ seg,
+                                                const uint32_t* img, int doc_local, int64_t doc, bool in,
+                                                uint64_t (&cv)[PA_MAX_EXPR_COLUMNS]) {
+  const int nc = E->num_cols;
+  uint32_t fmask = 0;
+  uint32_t id[PA_MAX_EXPR_COLUMNS];
+#pragma unroll
+  for (int c = 0; c < PA_MAX_EXPR_COLUMNS; ++c) {
+    cv[c] = 0;
+    id[c] = 0;
+    if (c >= nc) continue;
+    const DevCol& col = seg->cols[E->col_slot[c]];
+    if (col.vtype == PA_FLOAT || col.vtype == PA_DOUBLE) fmask |= 1u << c;
+    if (!in) continue;
+    if (col.kind == COL_SV_DICT) {
+      id[c] = decode_dict_id(col, img, doc_local, doc);
+    } else {
+      switch (col.vtype) {
+        case PA_INT: cv[c] = (uint64_t)(int64_t)gp((const int32_t*)col.raw)[doc]; break;
+        case PA_LONG: cv[c] = (uint64_t)gp((const int64_t*)col.raw)[doc]; break;
+        case PA_FLOAT: cv[c] = __builtin_bit_cast(uint64_t, (double)gp((const float*)col.raw)[doc]); break;
+        default: cv[c] = (uint64_t)gp((const int64_t*)col.raw)[doc]; break;
+      }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < PA_MAX_EXPR_COLUMNS; ++c) {
+    if (c >= nc || !in) continue;
+    const DevCol& col = seg->cols[E->col_slot[c]];
+    if (col.kind != COL_SV_DICT) continue;
+    // (dict_i64 holds int64 values, dict_f64 doubles: 64 bits of the column's family either way)
+    cv[c] = ((fmask >> c) & 1u) ? (uint64_t)gp((const int64_t*)col.dict_f64)[id[c]] : (uint64_t)gp(col.dict_i64)[id[c]];
+  }
+  return fmask;
+}
+
+// Evaluate phase: one program over the gathered values; returns the result's 64 bits (a double's, or the int64).
+__device__ __forceinline__ uint64_t expr_eval(const ExprProg& P, const uint64_t (&cv)[PA_MAX_EXPR_COLUMNS],
+                                              uint32_t fmask) {
+  uint64_t r[PA_MAX_EXPR_REGS];
+#pragma unroll
+  for (int k = 0; k < PA_MAX_EXPR_REGS; ++k) r[k] = 0;
+  uint64_t last = 0;
+  const int n = P.num_ops;
+  for (int o = 0; o < n; ++o) {
+    const ExprOp& X = P.ops[o];
+    const int op = X.op;
+    uint64_t out;
+    if (op == PA_EXPR_LOAD_COL) {
+      const uint64_t x = expr_get(cv, X.a);
+      const bool fl = (fmask >> X.a) & 1u;
+      if (X.b == PA_EXPR_DOUBLE)
+        out = fl ? x : __builtin_bit_cast(uint64_t, (double)(int64_t)x);
+      else
+        out = fl ? (uint64_t)java_d2l(__builtin_bit_cast(double, x)) : x;
+    } else {
+      const uint64_t ab = X.a_kind == PA_EXPR_ARG_REG ? expr_get(r, X.a) : (uint64_t)X.a_imm;
+      if (op <= PA_EXPR_MOD) {
+        const uint64_t bb = X.b_kind == PA_EXPR_ARG_REG ? expr_get(r, X.b) : (uint64_t)X.b_imm;
+        const double a = __builtin_bit_cast(double, ab), b = __builtin_bit_cast(double, bb);
+        double d;
+        if (op == PA_EXPR_ADD) d = a + b;
+        else if (op == PA_EXPR_SUB) d = a - b;
+        else if (op == PA_EXPR_MUL) d = a * b;
+        else if (op == PA_EXPR_DIV) d = a / b;
+        else d = fmod(a, b);
+        out = __builtin_bit_cast(uint64_t, d);
+      } else if (op == PA_EXPR_ABS) {
+        out = ab & 0x7fffffffffffffffull;
+      } else if (op == PA_EXPR_CEIL) {
+        out = __builtin_bit_cast(uint64_t, ceil(__builtin_bit_cast(double, ab)));
+      } else if (op == PA_EXPR_FLOOR) {
+        out = __builtin_bit_cast(uint64_t, floor(__builtin_bit_cast(double, ab)));
+      } else if (op == PA_EXPR_D2L) {
+        out = (uint64_t)java_d2l(__builtin_bit_cast(double, ab));
+      } else if (op == PA_EXPR_L2D) {
+        out = __builtin_bit_cast(uint64_t, (double)(int64_t)ab);
+      } else if (op == PA_EXPR_TCONV_DIV) {
+        out = (uint64_t)((int64_t)ab / X.b_imm);
+      } else {
+        out = (uint64_t)tconv_mul((int64_t)ab, X.b_imm);
+      }
+    }
+    expr_set(r, X.dst, out);
+    last = out;
+  }
+  return last;
+}
+
+// One 64-doc step of a query with expressions: gather, evaluate every program, then accumulate_step with the results.
+template <int STRAT>
+__device__ __forceinline__ void expr_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                          const uint32_t* img, int doc_local, int64_t doc, uint64_t matched, int lane,
+                                          const Acc<STRAT>& acc) {
+  ExprVals ev;
+  ev.E = uniform_ptr(q->expr);
+  const bool mine = (matched >> lane) & 1ull;
+  uint64_t cv[PA_MAX_EXPR_COLUMNS];
+  const uint32_t fmask = expr_gather(ev.E, seg, img, doc_local, doc, mine, cv);
+  const int ne = ev.E->num_exprs;
+#pragma unroll
+  for (int e = 0; e < PA_MAX_EXPRS; ++e) ev.res[e] = 0;
+  for (int e = 0; e < ne; ++e) {  // (not unrolled: one copy of the evaluator in the kernel)
+    uint64_t x = expr_eval(ev.E->progs[e], cv, fmask);
+    // (one NaN: doubleToLongBits, for the group key; SUM / MIN / MAX treat every NaN alike)
+    if (ev.E->progs[e].result_type == PA_EXPR_DOUBLE && (x & 0x7fffffffffffffffull) > 0x7ff0000000000000ull)
+      x = 0x7ff8000000000000ull;
+    expr_set(ev.res, e, x);
+  }
+  accumulate_step<STRAT>(q, seg, img, doc_local, doc, matched, lane, acc, &ev);
+}
+
 // The rare part of a tile (some doc survived the eager clauses): lazy clauses per surviving doc, then aggregation.
 // Returns the docs that matched.
 // LM: doc of bit i of lane l = 32l + i (lane-major tile), else 64i + l.
@@ -3362,6 +3563,13 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
   } else if constexpr (is_filtered(STRAT)) {
     static_assert(!LM, "filtered aggregations run step-major tiles");
     filtered_tile<STRAT, STEPS>(q, seg, img, doc_base, m, lane, acc);
+  } else if constexpr (is_expr(STRAT)) {
+    static_assert(!LM, "expression queries run step-major tiles");
+    for (int i = 0; i < STEPS; ++i) {
+      const uint64_t sm = __ballot((m >> i) & 1u);
+      if (sm == 0) continue;
+      expr_step<STRAT>(q, seg, img, i * kWave + lane, doc_base + i * kWave + lane, sm, lane, acc);
+    }
   } else if constexpr (is_lane(STRAT)) {
     if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_tile<LM, STEPS, STRAT>(q, seg, img, doc_base, m, lane, la, lds);
   } else if constexpr (is_pcount(STRAT) || is_pemit(STRAT)) {
@@ -3694,6 +3902,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (STRAT == STRAT_SELECT) sel_state_init(la, smem, wave);
   if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_zero<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_EXPR_LDS) lds_acc_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_zero<WGS>(q, lds_acc);
   const int64_t T = q->total_wtiles;
   const int64_t W = (int64_t)gridDim.x * WPW;
@@ -3849,6 +4058,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (STRAT == STRAT_SELECT) sel_counters_flush(q, la, lane);
   if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_flush<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_flush<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_EXPR_LDS) lds_acc_flush<WGS>(q, lds_acc);
   if (!is_pemit(STRAT)) {  // (the partitioned count pass counts numDocsScanned; its emit pass sees the same docs)
     const int64_t wm = wave_sum_i64((int64_t)matched);
     if (lane == 0 && wm != 0) __hip_atomic_fetch_add(gp(q->matched_docs), (unsigned long long)wm, RLX);
@@ -3878,5 +4088,6 @@ const void* scan_fn_gdense(int strategy, int lm);          // pa_scan_gdense.hip
 const void* scan_fn_select(int strategy, int steps);       // pa_scan_select.hip: STRAT_SELECT (step-major tiles)
 const void* scan_fn_distinct(int strategy, int steps);     // pa_scan_distinct.hip: STRAT_DISTINCT* (step-major tiles)
 const void* scan_fn_filtered(int strategy, int steps);     // pa_scan_filtered.hip: STRAT_FILTERED* (step-major tiles)
+const void* scan_fn_expr(int strategy, int steps);         // pa_scan_expr.hip: STRAT_EXPR* (step-major tiles)
 
 }  // namespace pa

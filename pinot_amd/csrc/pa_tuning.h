@@ -75,7 +75,14 @@
   /* filtered aggregations: 0 = device-scope atomics (STRAT_FILTERED), 1 = the workgroup-private LDS accumulators       \
      (STRAT_FILTERED_LDS) whenever they fit next to a tile ring (default: when they take at most 64 KiB and the lanes'  \
      union is dense, STRAT_LDS's rule) */                                                                               \
-  X(filtered_lds, -1, 0, 1, 0)
+  X(filtered_lds, -1, 0, 1, 0)                                                                                         \
+  /* transform expressions: 0 = device-scope atomics (STRAT_EXPR), 1 = the workgroup-private LDS accumulators           \
+     (STRAT_EXPR_LDS) whenever the key space is direct and they fit next to a tile ring (default: when they take at    \
+     most 64 KiB and the matching docs are dense, STRAT_LDS's rule) */                                                  \
+  X(expr_lds, -1, 0, 1, 0)                                                                                             \
+  /* hashed key spaces: the slot table holds at most this many slots (rounded down to a power of two; default: twice   \
+     the keys that can exist, up to 2^28). A small cap lets a small table reach the group-key table overflow report */  \
+  X(hash_slots_cap, -1, 1024, 1 << 28, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;

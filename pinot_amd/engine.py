@@ -22,6 +22,7 @@ import numpy as np
 from . import _lib as L
 from . import predicate as P
 from . import query as Q
+from . import transform as T
 from .hll import HyperLogLog, hash_value
 from .java_hash import java_hash_code
 from .optimizer import optimize_filter
@@ -371,8 +372,28 @@ class GpuQueryExecutor:
                 self.pa_agg_filter.append(cur[0])
             return acc_keys.index(ident)
 
+        # transform expressions (SUM(ADD(a, b)), GROUP BY timeConvert(...); transform.py): every distinct expression of
+        # the aggregation arguments and group-by items becomes one device program over a shared operand-column table
+        # (pa_query_set_expressions). An expression aggregation's GPU accumulator is keyed by column id -2 - its index.
+        self.exprs, self.programs, self.expr_columns = T.check_query(
+            q, {n: (c.data_type, bool(c.single_value)) for n, c in seg0.columns.items()})
+        expr_index = self.exprs.index
+
         for a in q.aggregations:
             fn = a.function
+            if isinstance(a.column, Q.Expr):
+                cid = -2 - expr_index(a.column)
+                self.agg_lane.append(-1)
+                cur[0] = -1
+                if fn in ("SUM", "AVG"):
+                    self.agg_map.append(acc_index((L.PA_AGG_SUM, cid, 0)))
+                elif fn == "MIN":
+                    self.agg_map.append(acc_index((L.PA_AGG_MIN, cid, 0)))
+                elif fn == "MAX":
+                    self.agg_map.append(acc_index((L.PA_AGG_MAX, cid, 0)))
+                else:
+                    self.agg_map.append((acc_index((L.PA_AGG_MIN, cid, 0)), acc_index((L.PA_AGG_MAX, cid, 0))))
+                continue
             if fn.endswith("MV") and seg0.column(a.column).single_value:
                 raise UnsupportedQuery("%s on single-value column %s" % (fn, a.column))
             lane = lane_of(a)
@@ -485,7 +506,18 @@ class GpuQueryExecutor:
         if spec.num_group_by > L.PA_MAX_GROUP_BY:
             raise UnsupportedQuery("too many group-by columns")
         self.raw_group_by = []
+        self.group_by_expr = []  # per group-by position: its expression's index, or -1
         for j, name in enumerate(q.group_by):
+            if isinstance(name, Q.Expr):
+                # grouped by the value's 64 bits, as a raw LONG / DOUBLE column is (NoDictionary*GroupKeyGenerator)
+                e = expr_index(name)
+                self.group_by_expr.append(e)
+                self.global_dicts.append(None)
+                self.raw_group_by.append(self.programs[e].result_type)
+                spec.group_by_columns[j] = 0
+                spec.group_by_cardinality[j] = 0
+                continue
+            self.group_by_expr.append(-1)
             has_dict = [s.column(name).has_dictionary for s in self.segs]
             if not any(has_dict):
                 # raw (no-dictionary) column: grouped by value through the hashed key space
@@ -513,8 +545,8 @@ class GpuQueryExecutor:
         for seg in self.segs:
             rm = []
             for j, name in enumerate(q.group_by):
-                d = seg.column(name).dictionary
                 gd = self.global_dicts[j]
+                d = None if gd is None else seg.column(name).dictionary
                 if gd is None or d is gd or (len(d) == len(gd) and np.array_equal(d, gd)):
                     rm.append(None)
                 else:
@@ -536,6 +568,12 @@ class GpuQueryExecutor:
             L.check(lib.pa_query_set_tuning(self.handle, name.encode(), int(value)), "pa_query_set_tuning")
         self._keep = []
         self._after_create()
+        if self.exprs:
+            if self.dev_filters:
+                raise UnsupportedQuery("transform expressions next to aggregation filters")
+            es = T.fill_spec(self.programs, [ids[c] for c in self.expr_columns],
+                             [-2 - cid if cid <= -2 else -1 for _, cid, _ in self.pa_aggs], self.group_by_expr)
+            L.check(lib.pa_query_set_expressions(self.handle, ctypes.byref(es)), "pa_query_set_expressions")
         if self.dev_filters:
             fs = L.AggFilterSpec()
             fs.num_filters = len(self.dev_filters)
@@ -588,8 +626,9 @@ class GpuQueryExecutor:
         try:
             L.check(lib.pa_query_prepare(self.handle), "pa_query_prepare")
         except L.PinotAmdError as e:
-            if self.dev_filters and getattr(e, "code", 0) == L.PA_EUNSUPPORTED:
-                raise UnsupportedQuery(str(e)) from None  # (what the library refuses of a filtered-aggregation query)
+            if (self.dev_filters or self.exprs) and getattr(e, "code", 0) == L.PA_EUNSUPPORTED:
+                # (what the library refuses of a query with aggregation filters or transform expressions)
+                raise UnsupportedQuery(str(e)) from None
             raise
         self.num_keys = int(lib.pa_query_num_keys(self.handle))
         hashed, shifts = ctypes.c_int32(), (ctypes.c_int32 * max(1, len(q.group_by)))()
@@ -658,7 +697,7 @@ class GpuQueryExecutor:
         out["plan"]["strategy"] = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane", 6: "lane", 7: "lane",
                                     8: "lds_dense", 9: "lds_dense", 10: "lds_dense", 11: "lds_dense", 12: "lds_dense",
                                     14: "lds_dense", 15: "lds_dense", 128: "select", 129: "distinct",
-                                    130: "distinct", 131: "filtered", 132: "filtered"}[code]
+                                    130: "distinct", 131: "filtered", 132: "filtered", 133: "expr", 134: "expr"}[code]
         out["plan"]["variant"] = STRATEGY_VARIANTS.get(code, str(code))
         out["plan"]["eager_literals"] = int(L.lib().pa_query_num_eager_literals(self.handle))
         out["plan"]["lane_major"] = int(L.lib().pa_query_lane_major(self.handle))
@@ -967,6 +1006,10 @@ class GpuQueryExecutor:
             res.num_entries_scanned_in_filter, res.num_entries_scanned_post_filter = self.execution_stats(
                 stream, res.num_docs_scanned)
         key_cols = [kc.tolist() for kc in self.key_values(keys)]
+        for j, e in enumerate(getattr(self, "group_by_expr", ())):
+            if e >= 0 and self.programs[e].result_type == T.DOUBLE:
+                # (one NaN key, -0.0 and 0.0 two: the reference's map compares doubleToLongBits)
+                key_cols[j] = [T.DoubleKey(v) for v in key_cols[j]]
         cols = []  # one python list per query aggregation
         hists = {}
         lane_counts = self.fetch_lane_counts(n, stream) if self.dev_filters and not self.match_none else None
@@ -1058,7 +1101,7 @@ class GpuQueryExecutor:
 STRATEGY_VARIANTS = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane_cnt", 6: "lane_raw", 7: "lane_dict",
                      8: "gdense4", 9: "gdense8", 10: "gdense12", 11: "gdense_rs12", 12: "gdense_rs8", 14: "gdense_lm8",
                      15: "gdense_lm16", 128: "select", 129: "distinct_lds", 130: "distinct_global",
-                     131: "filtered_lds", 132: "filtered_global"}
+                     131: "filtered_lds", 132: "filtered_global", 133: "expr_lds", 134: "expr_global"}
 
 
 class SelectionExecutor(GpuQueryExecutor):

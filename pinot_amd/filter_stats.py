@@ -472,6 +472,8 @@ def non_scan_plan(query, segment, match_all):
     for a in query.aggregations:
         if a.function == "COUNT":
             continue
+        if isinstance(a.column, Q.Expr):  # (only an identifier argument is answered from dictionary or metadata)
+            return False
         col = segment.column(a.column)
         if a.function in DICTIONARY_BASED and col.has_dictionary:
             continue
@@ -482,11 +484,14 @@ def non_scan_plan(query, segment, match_all):
 
 
 def projected_columns(query):
-    """Columns the ProjectionOperator reads: group-by columns and aggregation arguments (COUNT(*) reads none)."""
-    cols = list(query.group_by)
+    """Columns the ProjectionOperator reads: group-by columns and aggregation arguments (COUNT(*) reads none), a
+    transform expression counting as the distinct columns it reads (the TransformOperator sits on one projection of
+    them: AggregationOperator.java:86, GroupByOperator.java:146)."""
+    cols = []
+    for g in query.group_by:
+        Q.item_columns(g, cols)
     for a in query.aggregations:
-        if a.column is not None and a.column not in cols:
-            cols.append(a.column)
+        Q.item_columns(a.column, cols)
     return len(cols)
 
 

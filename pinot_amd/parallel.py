@@ -249,7 +249,8 @@ def wide_sum_columns_local(query, segments):
     else: pa_segment.hip pa_segment_add_raw_column / upload_dict)."""
     out = set()
     for a in query.aggregations:
-        if a.function not in SUM_FUNCTIONS or a.column in out:
+        # (a transform expression's SUM has one layout on every rank: a DOUBLE sum, or the exact pair of a LONG one)
+        if a.function not in SUM_FUNCTIONS or a.column in out or isinstance(a.column, Expr):
             continue
         for s in segments:
             c = s.column(a.column)
@@ -269,6 +270,8 @@ def hash_keys_bound_local(query, segments):
     for s in segments:
         n = s.num_docs
         for name in query.group_by:
+            if isinstance(name, Expr):  # (one key per doc at most, as a raw column)
+                continue
             c = s.column(name)
             if not c.single_value:
                 n = max(n, int(c.total_num_values)) * 2
@@ -292,7 +295,7 @@ class TableLayout:
                     hash_keys_bound=self.hash_keys_bound, schema=self.schema)
 
 
-from .query import DISTINCT_SET_FUNCTIONS as DISTINCT_FUNCTIONS, PERCENTILE_FUNCTIONS, query_columns  # noqa: E402
+from .query import DISTINCT_SET_FUNCTIONS as DISTINCT_FUNCTIONS, Expr, PERCENTILE_FUNCTIONS, query_columns  # noqa: E402
 
 
 def _encode_record(rec):
@@ -380,6 +383,8 @@ def table_layout(query, segments, group=None):
             c = s.column(name)
             local["schema"].setdefault(name, (c.data_type, bool(c.has_dictionary), bool(c.single_value)))
     for name in query.group_by:
+        if isinstance(name, Expr):  # (grouped by value bits: no dictionary to agree on)
+            continue
         ds = [s.column(name).dictionary for s in segments if s.column(name).has_dictionary]
         if ds:
             local["dicts"][name] = np.unique(np.concatenate(ds))
@@ -391,6 +396,8 @@ def table_layout(query, segments, group=None):
     gathered = all_gather_records(local, group)
     out = TableLayout()
     for name in query.group_by:
+        if isinstance(name, Expr):
+            continue
         parts = [g["dicts"][name] for g in gathered if name in g["dicts"]]
         if parts:
             out.dicts[name] = np.unique(np.concatenate(parts))

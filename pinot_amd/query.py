@@ -11,6 +11,9 @@ parser for the SQL subset the reference's query tests use on this path:
 
 filter: AND / OR / NOT / ( ) over  col = v | col != v | col <> v | col < v | col <= v | col > v | col >= v |
         col BETWEEN a AND b | col IN (...) | col NOT IN (...) | REGEXP_LIKE(col, 'regex') | col [NOT] LIKE 'pattern'
+An aggregation argument (of SUM / MIN / MAX / AVG / MINMAXRANGE) and a GROUP BY item (also in the select list and in
+ORDER BY) may be a transform expression (Expr): function calls fn(arg, ...), infix + - * / % (Calcite's plus / minus /
+times / divide / mod; * / % bind over + -, left-associative), parentheses, columns and literals. A plain column stays a str.
 REGEXP_LIKE / LIKE become RegexpLikePredicate as in RequestContextUtils.java:231-236 (LIKE through likeToRegexpLike).
 Comparison predicates become RangePredicate exactly as the reference's RequestContextUtils does
 (pinot-common/.../request/context/RequestContextUtils.java: >, >=, <, <=, BETWEEN -> RANGE).
@@ -227,6 +230,51 @@ def filter_columns(f, into):
     return into
 
 
+@dataclass(frozen=True)
+class Expr:
+    """A transform function call (pinot-common FunctionContext inside an ExpressionContext): fn is the canonical
+    function name (lower case, underscores removed: `add`, `plus` for infix +, `timeconvert`), args are Expr nodes and
+    the leaves ("id", column name) / ("lit", text as written)."""
+    fn: str
+    args: Tuple
+
+    def __str__(self):
+        """ExpressionContext.toString: fn(arg,arg) without spaces, literals in single quotes (LiteralContext.toString)
+        — the result column name of an aggregation over it (`max(add(column1,column9))`,
+        ForwardIndexDisabledSingleValueQueriesTest.java:1604) and the group-key column name."""
+        return "%s(%s)" % (self.fn, ",".join(
+            str(a) if isinstance(a, Expr) else (a[1] if a[0] == "id" else "'%s'" % a[1]) for a in self.args))
+
+    def columns(self, into=None):
+        """The columns the expression reads, in first-use order."""
+        into = [] if into is None else into
+        for a in self.args:
+            if isinstance(a, Expr):
+                a.columns(into)
+            elif a[0] == "id" and a[1] not in into:
+                into.append(a[1])
+        return into
+
+
+def item_columns(item, into):
+    """Adds the column(s) behind an aggregation argument or group-by item (a column name or an Expr) to `into`."""
+    for c in (item.columns() if isinstance(item, Expr) else ([item] if item else [])):
+        if c not in into:
+            into.add(c) if isinstance(into, set) else into.append(c)
+    return into
+
+
+# names that start a transform expression in a select list or ORDER BY (every other call there is an aggregation):
+# TransformFunctionType's arithmetic, math and date-time functions, whether the engine runs them or refuses them
+TRANSFORM_NAMES = frozenset((
+    "add plus sub minus mult times div divide mod abs ceil ceiling floor exp ln log log2 log10 sign sqrt power pow "
+    "rounddecimal truncate least greatest timeconvert datetimeconvert datetrunc cast case year month day hour minute "
+    "second tojsonmapstr jsonextractscalar arraylength valuein upper lower concat substr").split())
+_INFIX = {"+": "plus", "-": "minus", "*": "times", "/": "divide", "%": "mod"}
+# an identifier token spelled like one of these is never the left operand of a subtraction
+_KEYWORDS = frozenset("AND OR NOT BETWEEN IN LIKE WHERE BY SELECT LIMIT OFFSET TOP DISTINCT AS WHEN THEN ELSE".split())
+
+
 def base_function(fn):
     """Merge/extract semantics of a function: the *MV forms behave like their single-value form, COUNTMV like COUNT."""
     return fn[:-2] if fn.endswith("MV") else fn
@@ -235,7 +283,7 @@ def base_function(fn):
 @dataclass(frozen=True)
 class Aggregation:
     function: str              # COUNT SUM MIN MAX AVG DISTINCTCOUNTHLL and the *MV forms
-    column: Optional[str] = None
+    column: object = None      # the column's name, or the transform expression (Expr) it aggregates
     log2m: int = DEFAULT_HLL_LOG2M
     percentile: float = -1.0   # PERCENTILE / PERCENTILEMV: 0..100
     version: int = 0           # PERCENTILE spelling: 0 = PERCENTILE<digits>(col), 1 = PERCENTILE(col, p)
@@ -276,7 +324,7 @@ class Query:
     aggregations: List[Aggregation]
     aliases: List[Optional[str]] = field(default_factory=list)
     filter: object = None
-    group_by: List[str] = field(default_factory=list)
+    group_by: List[object] = field(default_factory=list)   # column names and transform expressions (Expr)
     order_by: List[OrderBy] = field(default_factory=list)
     limit: int = 10
     options: dict = field(default_factory=dict)
@@ -306,10 +354,11 @@ class Query:
         return int(self.options.get("minServerGroupTrimSize", DEFAULT_MIN_SERVER_GROUP_TRIM_SIZE))
 
     def columns(self):
-        cols = set(self.group_by)
+        cols = set()
+        for g in self.group_by:
+            item_columns(g, cols)
         for a in self.aggregations:
-            if a.column:
-                cols.add(a.column)
+            item_columns(a.column, cols)
             filter_columns(a.filter, cols)
         if self.is_selection or self.is_distinct:
             cols.update(self.select_columns)
@@ -332,7 +381,7 @@ class Query:
 # ------------------------------------------------------------------ SQL subset parser
 _TOKEN = re.compile(r"\s*(?:(?P<num>-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?)|(?P<str>'(?:[^']|'')*')|"
                     r"(?P<qid>\"(?:[^\"]|\"\")*\")|"
-                    r"(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*)|(?P<id>[A-Za-z_][A-Za-z0-9_\.]*))")
+                    r"(?P<op><>|!=|<=|>=|=|<|>|\(|\)|,|\*|\+|-|/|%)|(?P<id>[A-Za-z_][A-Za-z0-9_\.]*))")
 
 
 def _tokenize(sql):
@@ -344,7 +393,14 @@ def _tokenize(sql):
             raise ValueError("cannot tokenize at: %r" % sql[pos:pos + 20])
         pos = m.end()
         if m.group("num") is not None:
-            out.append(("lit", m.group("num")))
+            num = m.group("num")
+            prev = out[-1] if out else (None, None)
+            if num[0] == "-" and (prev[0] == "lit" or prev == ("op", ")") or
+                                  (prev[0] == "id" and prev[1].upper() not in _KEYWORDS)):
+                # `a -1`, `a-1`, `(a) -1`: a subtraction, not a negative literal after an operand
+                out.append(("op", "-"))
+                num = num[1:]
+            out.append(("lit", num))
         elif m.group("str") is not None:
             out.append(("lit", m.group("str")[1:-1].replace("''", "'")))
         elif m.group("qid") is not None:  # "quoted identifier"
@@ -434,7 +490,7 @@ class _Parser:
             return Aggregation("COUNT")
         if fn.startswith("PERCENTILE"):
             return self.percentile(fn)
-        col = self.ident()
+        col = self.item()
         log2m = DEFAULT_HLL_LOG2M
         if self.op(","):
             log2m = int(self.literal())
@@ -443,12 +499,81 @@ class _Parser:
             raise ValueError("unsupported aggregation %s" % fn)
         return Aggregation(fn, col, log2m)
 
+    # ---- transform expressions
+    def item(self):
+        """An aggregation argument or group-by item: a column name (str), or an Expr."""
+        e = self.expr()
+        if isinstance(e, Expr):
+            return e
+        if e[0] != "id":
+            raise ValueError("expected a column or an expression, not the literal %r" % (e[1],))
+        return e[1]
+
+    def expr(self):
+        left = self.term()
+        while self.peek() in (("op", "+"), ("op", "-")):
+            sym = self.peek()[1]
+            self.i += 1
+            left = Expr(_INFIX[sym], (left, self.term()))
+        return left
+
+    def term(self):
+        left = self.primary()
+        while self.peek() in (("op", "*"), ("op", "/"), ("op", "%")):
+            sym = self.peek()[1]
+            self.i += 1
+            left = Expr(_INFIX[sym], (left, self.primary()))
+        return left
+
+    def primary(self):
+        tok, nxt = self.peek(), self.peek(1)
+        if self.op("("):
+            e = self.expr()
+            self.expect_op(")")
+            return e
+        if tok[0] == "lit":
+            self.i += 1
+            return tok
+        if tok[0] != "id":
+            raise ValueError("expected a column, literal or function call at %r" % (tok,))
+        self.i += 1
+        name = tok[1].replace("_", "").lower()
+        if name == "case" and nxt != ("op", "("):
+            # CASE ... END: kept opaque (the engine refuses it); nested CASEs balance
+            depth = 1
+            while depth:
+                t = self.peek()
+                if t[0] is None:
+                    raise ValueError("CASE without END")
+                self.i += 1
+                if t[0] == "id":
+                    depth += (t[1].upper() == "CASE") - (t[1].upper() == "END")
+            return Expr("case", ())
+        if nxt != ("op", "("):
+            return tok
+        self.i += 1
+        args = []
+        if not self.op(")"):
+            while True:
+                args.append(self.expr())
+                if name == "cast" and self.kw("AS"):
+                    args.append(("lit", self.ident()))
+                if not self.op(","):
+                    break
+            self.expect_op(")")
+        return Expr(name, tuple(args))
+
+    def is_aggregation_call(self):
+        """The next tokens start an aggregation: name( where the name is no transform function."""
+        tok, nxt = self.peek(), self.peek(1)
+        return tok[0] == "id" and nxt == ("op", "(") and tok[1].replace("_", "").lower() not in TRANSFORM_NAMES
+
     def percentile(self, fn):
         """AggregationFunctionFactory.java:66-175 for the exact percentile: PERCENTILE<digits>(col) and
         PERCENTILE<digits>MV(col) (version 0), PERCENTILE(col, p) and PERCENTILEMV(col, p) (version 1, p a number or a
         quoted number); every other PERCENTILE* name (EST, TDIGEST, KLL, RAW...) is not on this path."""
         rest = fn[len("PERCENTILE"):]
-        col = self.ident()
+        col = self.item()
         args = []
         while self.op(","):
             args.append(self.literal())
@@ -560,8 +685,8 @@ class _Parser:
                 raise ValueError("DISTINCT takes plain columns (no aggregations, no *): %r" % (tok,))
             if self.op("*"):
                 star = True
-            elif tok[0] == "id" and not (nxt[0] == "op" and nxt[1] == "("):
-                plain_cols.append(self.ident())  # group-by column in the select list
+            elif not self.is_aggregation_call():
+                plain_cols.append(self.item())  # group-by column or expression in the select list
                 if self.peek()[0] == "id" and self.peek()[1].upper() == "FILTER":
                     raise ValueError("FILTER clause: it follows an aggregation, not the column %r" % plain_cols[-1])
             else:
@@ -587,20 +712,20 @@ class _Parser:
             q.filter = self.filter_or()
         if self.kw("GROUP"):
             self.expect_kw("BY")
-            q.group_by.append(self.ident())
+            q.group_by.append(self.item())
             while self.op(","):
-                q.group_by.append(self.ident())
+                q.group_by.append(self.item())
         if self.kw("ORDER"):
             self.expect_kw("BY")
             while True:
                 tok, nxt = self.peek(), self.peek(1)
-                if tok[0] == "id" and nxt[0] == "op" and nxt[1] == "(":
+                if self.is_aggregation_call():
                     expr = self.aggregation()
                     if expr not in aggs:  # ORDER BY aggregation absent from the select list: computed, not output
                         aggs.append(expr)
                         aliases.append(None)
                 else:
-                    name = self.ident()
+                    name = self.item()
                     expr = name
                     for a, al in zip(aggs, aliases):
                         if al == name:
@@ -678,8 +803,7 @@ def query_columns(query):
         walk(query.filter)
     for n in list(query.group_by) + [a.column for a in query.aggregations if a.column] + \
             (list(query.select_columns) if query.is_distinct else []):
-        if n not in names:
-            names.append(n)
+        item_columns(n, names)
     for a in query.aggregations:
         filter_columns(a.filter, names)
     return names
