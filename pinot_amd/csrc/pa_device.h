@@ -54,18 +54,18 @@ enum Strategy : int32_t {
   STRAT_PCOUNT_MV = 13,
   // STRAT_GDENSE over the LDS-DMA ring with the lane-major walk (gdl_tile): 8- / 16-wave workgroups
   STRAT_GDENSE_LM8 = 14, STRAT_GDENSE_LM16 = 15,
-  // selection (SELECT columns ... ORDER BY ... LIMIT): filter + per-wave top-K candidates (pa_scan.h "selection");
+  // selection (SELECT columns ... ORDER BY ... LIMIT): filter + per-wave top-K candidates (pa_strat_select.h "selection");
   // its code lies above the emit variants' range (is_pemit)
   STRAT_SELECT = 128,
-  // distinct (SELECT DISTINCT ...): filter + one bit per key of the direct key space (pa_scan.h "distinct"): the
+  // distinct (SELECT DISTINCT ...): filter + one bit per key of the direct key space (pa_strat_distinct.h "distinct"): the
   // workgroup-private LDS bitmap, flushed once per workgroup, or test-before-set on the bitmap in HBM
   STRAT_DISTINCT_LDS = 129, STRAT_DISTINCT = 130,
   // filtered aggregations (AGG(x) FILTER (WHERE ...)): filter + one mask per aggregation filter ("lane") over the
-  // surviving docs + per-lane aggregation (pa_scan.h "filtered aggregations"): workgroup-private accumulators in LDS,
+  // surviving docs + per-lane aggregation (pa_strat_filtered.h "filtered aggregations"): workgroup-private accumulators in LDS,
   // flushed once per workgroup, or device-scope atomics
   STRAT_FILTERED_LDS = 131, STRAT_FILTERED = 132,
   // transform expressions (SUM(ADD(a, b)), GROUP BY timeConvert(...)): filter + one gather of the operand columns + the
-  // expression programs per matching doc (pa_scan.h "expressions"): workgroup-private accumulators in LDS over a direct
+  // expression programs per matching doc (pa_strat_expr.h "expressions"): workgroup-private accumulators in LDS over a direct
   // key space, flushed once per workgroup, or device-scope atomics (direct or hashed key space)
   STRAT_EXPR_LDS = 133, STRAT_EXPR = 134
 };

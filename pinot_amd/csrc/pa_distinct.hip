@@ -1,5 +1,5 @@
-// Distinct queries (include/pinot_amd.h "distinct queries"): what follows the scan's key-presence bitmap (pa_scan.h
-// "distinct"), and their host side.
+// Distinct queries (include/pinot_amd.h "distinct queries"): what follows the scan's key-presence bitmap
+// (pa_strat_distinct.h "distinct"), and their host side.
 //
 // Finish. The rows are the first min(limit, P) present keys under the completed order (DstOrder). When that order is
 // the raw key's own digit order, the rows are the first set bits of the scan's bitmap: per block of bitmap words a
@@ -8,7 +8,7 @@
 // sets one bit of a second bitmap of the same size, and the same rank pass over that bitmap gives the rows in final
 // order: ordering P present keys costs one pass over the key space's bits, whatever the limit.
 #include "pa_host.h"
-#include "pa_scan.h"
+#include "pa_strat_distinct.h"
 
 namespace pa {
 

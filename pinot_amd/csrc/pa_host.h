@@ -333,7 +333,7 @@ struct pa_query {
   DstOrder dst_order{};
   bool dst_key_order = false;
   DevBuf dst_counts, dst_bits2, dst_rows;
-  // filtered aggregations (pa_query_set_agg_filters; pa_scan.h "filtered aggregations"): the spec, every filter's CNF
+  // filtered aggregations (pa_query_set_agg_filters; pa_strat_filtered.h "filtered aggregations"): the spec, every filter's CNF
   // (literals clause-major over the spec's leaves, with their clause ends), the descriptor the scan reads with its
   // device copy, every segment's DevLeafs of the lanes' literals, the per-(segment, lane) doc counters and the
   // fetched groups' keys + lane counts (grown on demand); the PA_ACC_LANE_COUNT_U64 section's index
@@ -346,7 +346,7 @@ struct pa_query {
   DevBuf filt_desc, filt_leaves, filt_seg_docs, lane_buf;
   int lane_section = -1;
   std::vector<int64_t> filt_seg_docs_host;  // filt_seg_docs as the last fetch read it ([nseg][num_filters + 1])
-  // transform expressions (pa_query_set_expressions; pa_scan.h "expressions"): the validated spec, and the descriptor
+  // transform expressions (pa_query_set_expressions; pa_strat_expr.h "expressions"): the validated spec, and the descriptor
   // the scan reads with its device copy
   bool is_expr = false;
   pa_expr_spec expr_spec{};

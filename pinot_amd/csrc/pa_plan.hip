@@ -1192,7 +1192,7 @@ int expr_check_spec(const pa_query_spec& s, const pa_expr_spec& e) {
   return PA_OK;
 }
 
-// An expression query against what the scan's evaluator covers (pa_scan.h "expressions").
+// An expression query against what the scan's evaluator covers (pa_strat_expr.h "expressions").
 int expr_validate(pa_query* q, Prep& P) {
   const pa_query_spec& s = q->spec;
   if (q->limit_mode || q->limit_walk)
@@ -1241,7 +1241,7 @@ int expr_plan(pa_query* q, const Prep& P) {
   return PA_OK;
 }
 
-// A filtered-aggregation query against what the scan's lane code covers (pa_scan.h "filtered aggregations").
+// A filtered-aggregation query against what the scan's lane code covers (pa_strat_filtered.h "filtered aggregations").
 int filtered_validate(pa_query* q, Prep& P) {
   const pa_query_spec& s = q->spec;
   if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "aggregation filters on a selection or distinct query");

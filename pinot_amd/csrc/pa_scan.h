@@ -1,6 +1,7 @@
 // Device code of the fused scan kernel (gfx950 / CDNA4 only): included by the translation units that instantiate its
-// variants (pa_scan_std.hip, pa_scan_global.hip, pa_scan_lane_*.hip, pa_scan_part_*.hip, pa_scan_select.hip), by
-// pa_gdense.h and pa_select.hip for the helpers they share with it, and by pa_kernels.hip (the other kernels).
+// variants (pa_scan_std.hip, pa_scan_global.hip, pa_scan_part_*.hip; the others through the pa_strat_*.h of their
+// strategy, see "strategies in headers of their own" below), by pa_gdense.h for the helpers it shares with it, and by
+// pa_kernels.hip (the other kernels).
 //
 // HIP kernels of the segment query hot path.
 //
@@ -444,7 +445,7 @@ __device__ __forceinline__ void expr_set(uint64_t (&v)[PA_MAX_EXPR_REGS], int i,
     v[k] = (x & m) | (v[k] & ~m);
   }
 }
-// What expr_step hands accumulate_step (pa_scan.h "expressions"): the programs' descriptor and their results for this
+// What expr_step hands accumulate_step (pa_strat_expr.h "expressions"): the programs' descriptor and their results for this
 // lane's doc.
 struct ExprVals {
   const ExprDesc* E;
@@ -2317,1201 +2318,57 @@ __device__ __forceinline__ uint32_t admitted_docs(const DevQuery* __restrict__ q
   return m;
 }
 
-// ---------------------------------------------------------------- aggregation-only queries (STRAT_LANE)
-// Every lane keeps its own running SUM / MIN / MAX of aggregation a in (r0[a], r1[a]) for the whole kernel (COUNT is the
-// filter's own doc count): SUM over int32 values r0 += v; over 64-bit values the exact split pair r0 += low 32 bits
-// (unsigned), r1 += v >> 32 (a 96-bit total, like PA_ACC_SUM_I64X2); over FLOAT/DOUBLE r0 holds the bits of a double
-// sum; MIN / MAX r0 = running min / max (doubles in the order-preserving encoding). The wave reduces them once, at the
-// end of the kernel (lane_acc_flush). Reference: AggregationOperator -> SumAggregationFunction.aggregate (a running sum
-// over the block's values), Min/MaxAggregationFunction.aggregate.
-// MIN / MAX over a sorted dictionary run on dictIds (rid[a]: the lane's min / max dictId within the current segment),
-// folded into r0 as a value at the end of every segment run (lane_acc_segment_end).
-typedef __attribute__((address_space(3))) int64_t lds_i64_t;
-__device__ __forceinline__ void la_get(const WaveState& la, int a, int64_t& r0, int64_t& r1) {
-  const lds_i64_t* p = (const lds_i64_t*)(uintptr_t)(la.pair + (uint32_t)a * la.astr);
-  r0 = p[0];
-  r1 = p[1];
-}
-__device__ __forceinline__ void la_set(const WaveState& la, int a, int64_t r0, int64_t r1) {
-  lds_i64_t* p = (lds_i64_t*)(uintptr_t)(la.pair + (uint32_t)a * la.astr);
-  p[0] = r0;
-  p[1] = r1;
-}
-__device__ __forceinline__ uint32_t la_rid(const WaveState& la, int a) {
-  return *(const lds_u32_t*)(uintptr_t)(la.id + (uint32_t)a * (la.astr >> 2));
-}
-__device__ __forceinline__ void la_set_rid(const WaveState& la, int a, uint32_t v) {
-  *(lds_u32_t*)(uintptr_t)(la.id + (uint32_t)a * (la.astr >> 2)) = v;
-}
-
-__device__ __forceinline__ uint32_t rid_init(int t) { return t == PA_AGG_MIN ? 0xffffffffu : 0u; }
-
+// ---------------------------------------------------------------- strategies in headers of their own
+// The lane, selection, distinct, filtered-aggregation and expression strategies live in pa_strat_*.h, which this header
+// does not include: their entry points are declared here, each call below sits in an `if constexpr` on the strategy,
+// and a unit includes the pa_strat_*.h of the strategies it instantiates (each includes this header). An edit to one of
+// them so rebuilds that strategy's units only.
+// pa_strat_lane.h
 __device__ __forceinline__ void lane_acc_init(const DevQuery* __restrict__ q, WaveState& la, const void* lds_area,
-                                              int wgs) {
-  la.astr = 16u * (uint32_t)wgs;
-  la.pair = lds_addr(lds_area) + 16u * threadIdx.x;
-  la.id = lds_addr(lds_area) + (uint32_t)q->num_aggs * la.astr + 4u * threadIdx.x;
-  la.idm = 0;
-  for (int a = 0; a < q->num_aggs && a < kLaneAggs; ++a) {
-    const int t = q->aggs[a].type;
-    la_set(la, a, t == PA_AGG_MIN ? INT64_MAX : (t == PA_AGG_MAX ? INT64_MIN : 0), 0);
-    la_set_rid(la, a, rid_init(t));
-  }
-}
-
-// Lane-major fast path modes (lane_agg_lm)
-enum LaneMode : int { LM_SUM_INT = 0, LM_SUM_LONG = 1, LM_SUM_DOUBLE = 2, LM_MIN_ID = 3, LM_MAX_ID = 4 };
-
-// One aggregation over the 32 docs of this lane in a lane-major tile (docs 32*lane + i, match bit i of m) from a staged
-// dictionary column of NB-bit ids: the lane's NB stream words are read once and every id is a constant-shift extract.
-// SUM: the value is a buffer load of dict[id] with a buffer resource bounded by the dictionary, and a doc that does not
-// match asks for index 0xffffffff (its bit of ~m spread by a signed bitfield extract, ORed into the id): out of range,
-// so the load returns 0 — no per-doc branch or select. MIN_ID / MAX_ID track the smallest / largest matching dictId
-// (0xffffffff is neutral under unsigned min; a non-matching id is ANDed to 0 for max).
-template <int NB>
-__device__ __forceinline__ void lane_agg_lm(uint32_t region_lds, int lane, uint32_t m, int mode,
-                                            __amdgpu_buffer_rsrc_t dict, int64_t& r0, int64_t& r1, uint32_t& rid) {
-  const lds_u32_t* p = (const lds_u32_t*)(uintptr_t)(region_lds + (uint32_t)lane * (uint32_t)(NB * 4));
-  constexpr int H = NB > 16 ? 2 : 1;  // halves of 16 docs for wide columns (live stream words stay ~NB/2 + 1)
-  constexpr int DPH = 32 / H;
-  const uint32_t nm = ~m;
-#pragma unroll
-  for (int h = 0; h < H; ++h) {
-    constexpr int WMAX = (DPH * NB + 31) / 32 + 1;
-    const int wlo = (h * DPH * NB) >> 5;
-    uint32_t w[WMAX];
-#pragma unroll
-    for (int j = 0; j < WMAX; ++j) w[j] = (wlo + j < NB) ? p[wlo + j] : 0u;
-    auto id_of = [&](int i) -> uint32_t {
-      const int s = i * NB, j = (s >> 5) - wlo, o = s & 31;
-      if (o + NB <= 32) return __builtin_amdgcn_ubfe(w[j], (uint32_t)(32 - o - NB), (uint32_t)NB);
-      return __builtin_amdgcn_alignbit(w[j], w[(j + 1 < WMAX) ? j + 1 : j], 32 - o) >> (32 - NB);
-    };
-    if (mode <= LM_SUM_DOUBLE) {
-      uint64_t v[DPH];
-#pragma unroll
-      for (int k = 0; k < DPH; ++k) {
-        const int i = h * DPH + k;
-        const uint32_t off = (id_of(i) << 3) | (uint32_t)__builtin_amdgcn_sbfe((int)nm, (uint32_t)i, 1u);
-        v[k] = __builtin_bit_cast(uint64_t, __builtin_amdgcn_raw_buffer_load_b64(dict, off, 0, 0));
-      }
-      if (mode == LM_SUM_INT) {
-#pragma unroll
-        for (int k = 0; k < DPH; ++k) r0 += (int64_t)v[k];
-      } else if (mode == LM_SUM_LONG) {
-#pragma unroll
-        for (int k = 0; k < DPH; ++k) {
-          r0 += (int64_t)(uint32_t)v[k];
-          r1 += (int64_t)v[k] >> 32;
-        }
-      } else {
-        double d = __builtin_bit_cast(double, r0);
-#pragma unroll
-        for (int k = 0; k < DPH; ++k) d += __builtin_bit_cast(double, v[k]);
-        r0 = __builtin_bit_cast(int64_t, d);
-      }
-    } else if (mode == LM_MIN_ID) {
-#pragma unroll
-      for (int k = 0; k < DPH; ++k) {
-        const int i = h * DPH + k;
-        rid = min(rid, id_of(i) | (uint32_t)__builtin_amdgcn_sbfe((int)nm, (uint32_t)i, 1u));
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < DPH; ++k) {
-        const int i = h * DPH + k;
-        rid = max(rid, id_of(i) & (uint32_t)__builtin_amdgcn_sbfe((int)m, (uint32_t)i, 1u));
-      }
-    }
-  }
-}
-
-__device__ __noinline__ void lane_agg_lm_any(int nb, uint32_t region_lds, int lane, uint32_t m, int mode,
-                                                __amdgpu_buffer_rsrc_t dict, int64_t& r0, int64_t& r1, uint32_t& rid) {
-  switch (nb) {
-#define PA_LA_CASE(N) \
-  case N: lane_agg_lm<N>(region_lds, lane, m, mode, dict, r0, r1, rid); break;
-    PA_LA_CASE(1) PA_LA_CASE(2) PA_LA_CASE(3) PA_LA_CASE(4) PA_LA_CASE(5) PA_LA_CASE(6) PA_LA_CASE(7) PA_LA_CASE(8)
-    PA_LA_CASE(9) PA_LA_CASE(10) PA_LA_CASE(11) PA_LA_CASE(12) PA_LA_CASE(13) PA_LA_CASE(14) PA_LA_CASE(15)
-    PA_LA_CASE(16) PA_LA_CASE(17) PA_LA_CASE(18) PA_LA_CASE(19) PA_LA_CASE(20) PA_LA_CASE(21) PA_LA_CASE(22)
-    PA_LA_CASE(23) PA_LA_CASE(24) PA_LA_CASE(25) PA_LA_CASE(26) PA_LA_CASE(27) PA_LA_CASE(28) PA_LA_CASE(29)
-    PA_LA_CASE(30) PA_LA_CASE(31)
-#undef PA_LA_CASE
-    default: break;
-  }
-}
-
-// End of a wave's run over one segment: MIN / MAX dictIds of the segment -> values, folded into r0 (only when the
-// lane kept some doc of the segment: a MAX dictId of 0 is otherwise meaningless).
+                                              int wgs);
 __device__ __forceinline__ void lane_acc_segment_end(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
-                                                     WaveState& la, bool any) {
-#pragma unroll
-  for (int a = 0; a < kLaneAggs; ++a) {
-    if (a >= q->num_aggs) break;
-    const int t = q->aggs[a].type;
-    if (t != PA_AGG_MIN && t != PA_AGG_MAX) continue;
-    const uint32_t id = la_rid(la, a);
-    la_set_rid(la, a, rid_init(t));
-    if (!((la.idm >> a) & 1u) || !any || (t == PA_AGG_MIN && id == 0xffffffffu)) continue;
-    const DevCol& c = seg->cols[q->aggs[a].slot];
-    const int64_t e = q->aggs[a].src == SRC_DOUBLE ? f64_order_encode(gp(c.dict_f64)[id]) : gp(c.dict_i64)[id];
-    int64_t r0, r1;
-    la_get(la, a, r0, r1);
-    la_set(la, a, t == PA_AGG_MIN ? (e < r0 ? e : r0) : (e > r0 ? e : r0), r1);
-  }
-  la.idm = 0;
-}
-
-// One value (int64, or double bits for SRC_DOUBLE) into a lane accumulator pair: SUM over int32-range values r0 += v;
-// 64-bit integer SUM as the exact split pair (r0 += low 32 bits unsigned, r1 += high 32 bits signed); double SUM in
-// r0's bits; MIN / MAX on the order-preserving encoding.
-__device__ __forceinline__ void lane_fold(int type, int src, uint64_t v, int64_t& r0, int64_t& r1) {
-  if (type == PA_AGG_SUM) {
-    if (src == SRC_INT) {
-      r0 += (int64_t)v;
-    } else if (src == SRC_LONG) {
-      r0 += (int64_t)(uint32_t)v;
-      r1 += (int64_t)v >> 32;
-    } else {
-      r0 = __builtin_bit_cast(int64_t, __builtin_bit_cast(double, r0) + __builtin_bit_cast(double, v));
-    }
-  } else {
-    const int64_t e = src == SRC_DOUBLE ? f64_order_encode(__builtin_bit_cast(double, v)) : (int64_t)v;
-    r0 = type == PA_AGG_MIN ? (e < r0 ? e : r0) : (e > r0 ? e : r0);
-  }
-}
-
-// A raw value as the 64-bit pattern lane_fold takes: INT sign-extended, FLOAT widened to double bits, LONG / DOUBLE as is.
-__device__ __forceinline__ uint64_t raw_bits(int vtype, uint64_t x) {
-  switch (vtype) {
-    case PA_INT: return (uint64_t)(int64_t)(int32_t)(uint32_t)x;
-    case PA_FLOAT: return __builtin_bit_cast(uint64_t, (double)__builtin_bit_cast(float, (uint32_t)x));
-    default: return x;
-  }
-}
-
-// Sparse lane-major tile (few matching docs): each lane walks its own set bits of m (doc 32*lane + i), four per batch so
-// their loads overlap; the wave loops max-popcount times instead of over all 32 docs. `load(i)` issues the value load of
-// doc i (nothing is consumed before all four are issued).
-template <class LOAD>
-__device__ __forceinline__ void lane_sparse(uint32_t m, int type, int src, LOAD load, int64_t& r0, int64_t& r1) {
-  while (__ballot(m != 0) != 0) {
-    bool on[4];
-    uint64_t v[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      on[k] = m != 0;
-      const int i = on[k] ? __builtin_ctz(m) : 0;
-      m &= m - 1u;
-      v[k] = on[k] ? load(i) : 0ull;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (on[k]) lane_fold(type, src, v[k], r0, r1);
-  }
-}
-
-// lane_sparse for a dictId histogram: every matching doc adds one to hist[dictId] (dec(i) = dictId of doc i); the
-// decodes of a batch of four are issued before their (non-returning) LDS adds.
-template <class DEC>
-__device__ __forceinline__ void lane_sparse_hist(uint32_t m, DEC dec, lds_u32_t* hist) {
-  while (__ballot(m != 0) != 0) {
-    bool on[4];
-    uint32_t id[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      on[k] = m != 0;
-      const int i = on[k] ? __builtin_ctz(m) : 0;
-      m &= m - 1u;
-      id[k] = on[k] ? dec(i) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (on[k]) __hip_atomic_fetch_add(hist + id[k], 1u, WG_RLX);
-  }
-}
-
-// lane_sparse for MIN / MAX of a sorted dictionary: the smallest / largest matching dictId (dec(i) = dictId of doc i).
-template <class DEC>
-__device__ __forceinline__ void lane_sparse_ids(uint32_t m, bool is_min, DEC dec, uint32_t& rid) {
-  while (__ballot(m != 0) != 0) {
-    bool on[4];
-    uint32_t id[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      on[k] = m != 0;
-      const int i = on[k] ? __builtin_ctz(m) : 0;
-      m &= m - 1u;
-      id[k] = on[k] ? dec(i) : 0u;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (on[k]) rid = is_min ? min(rid, id[k]) : max(rid, id[k]);
-  }
-}
-
-// Dense lane-major tile of a raw column of VB-byte values: the whole tile's values as coalesced 16-byte loads
-// (instruction k, lane l: docs VPL*(64k + l) .. + VPL-1 of the tile, VPL = 16 / VB), every value's match bit read from
-// the lane owning its doc in the lane-major layout (doc d: lane d >> 5, bit d & 31) by one ds_bpermute per
-// instruction. Non-matching values are skipped by a select (no per-doc branch). Raw columns are padded to whole wave
-// tiles, so the last tile's loads stay in bounds. 32 VGPRs of loads per batch, all issued before use.
-template <int VB>
-__device__ __forceinline__ void lane_raw_dense(const char* tile, uint32_t m, int lane, int vtype, int type, int src,
-                                               int64_t& r0, int64_t& r1) {
-  constexpr int VPL = 16 / VB;        // values per lane per instruction
-  constexpr int NI = 2048 * VB / 1024;  // instructions per tile
-  constexpr int KB = VB == 8 ? 4 : 8;
-  const AS1 u32x4* p = (const AS1 u32x4*)tile + lane;
-#pragma unroll
-  for (int k0 = 0; k0 < NI; k0 += KB) {
-    u32x4 w[KB];
-    uint32_t mb[KB];
-#pragma unroll
-    for (int k = 0; k < KB; ++k) {
-      w[k] = p[(k0 + k) * kWave];
-      // owner of doc VPL*(64k + l): lane 2*VPL*k + (VPL*l >> 5); its bits VPL*l & 31 .. + VPL-1
-      const int owner = 2 * VPL * (k0 + k) + ((VPL * lane) >> 5);
-      mb[k] = (uint32_t)__builtin_amdgcn_ds_bpermute(owner << 2, (int)m) >> ((VPL * lane) & 31);
-    }
-#pragma unroll
-    for (int k = 0; k < KB; ++k) {
-#pragma unroll
-      for (int j = 0; j < VPL; ++j) {
-        const uint64_t x = VB == 8 ? ((uint64_t)w[k][2 * j + 1] << 32) | w[k][2 * j] : (uint64_t)w[k][j];
-        const bool on = (mb[k] >> j) & 1u;
-        if (type == PA_AGG_SUM) {
-          lane_fold(type, src, on ? raw_bits(vtype, x) : 0ull, r0, r1);  // (+0 / +0.0 for a doc that does not match)
-        } else if (on) {
-          lane_fold(type, src, raw_bits(vtype, x), r0, r1);
-        }
-      }
-    }
-  }
-}
-
-// The matching docs (match words m) of one tile into the lane accumulators: per aggregation, 8 steps per batch — every
-// value load of the batch is issued before any is used (staged dictIds from the tile image, lazy ones and raw values from
-// HBM, then the dictionary gathers).
+                                                     WaveState& la, bool any);
 template <int LM, int STEPS, int STRAT>
 __device__ __forceinline__ void lane_acc_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                               const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
-                                              WaveState& la, unsigned char* lds) {
-  typedef const __attribute__((address_space(4))) DevSeg CSeg;
-  CSeg* cs = (CSeg*)(uintptr_t)seg;
-  auto local = [&](int i) { return LM ? 32 * lane + i : i * kWave + lane; };
-  constexpr int kB = 8;
-  const int na = q->num_aggs;
-  // matching docs of the tile: the wave's total and the largest count of one lane (sparse vs dense paths)
-  uint32_t tot = 0, mx = 0;
-  if constexpr (LM) {
-    tot = mx = (uint32_t)__builtin_popcount(m);
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      tot += (uint32_t)__shfl_xor((int)tot, o, kWave);
-      mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, kWave));
-    }
-    tot = (uint32_t)__builtin_amdgcn_readfirstlane((int)tot);
-    mx = (uint32_t)__builtin_amdgcn_readfirstlane((int)mx);
-  }
-  // one copy of the per-aggregation code (a loop that is not unrolled; the accumulators live in LDS): the unrolled form
-  // replicated every path per aggregation and spilled
-#pragma unroll 1
-  for (int a = 0; a < na && a < kLaneAggs; ++a) {
-    const int type = q->aggs[a].type;
-    if (type == PA_AGG_COUNT) continue;
-    const int slot = q->aggs[a].slot, src = q->aggs[a].src;
-    const int kind = cs->cols[slot].kind, vtype = cs->cols[slot].vtype;
-    const int loff = cs->cols[slot].lds_off, nb = cs->cols[slot].nbits;
-    const uint32_t* words = cs->cols[slot].words;
-    const uint64_t* dict = src == SRC_DOUBLE ? (const uint64_t*)cs->cols[slot].dict_f64
-                                             : (const uint64_t*)cs->cols[slot].dict_i64;
-    const void* raw = cs->cols[slot].raw;
-    int64_t r0, r1;
-    la_get(la, a, r0, r1);
-    uint32_t rid = la_rid(la, a);
-    do {  // (break: this aggregation is done)
-    if (STRAT == STRAT_LANE_DICT) {
-    } else if (LM && kind == COL_SV_RAW) {
-      // raw column: per-doc loads of the few matching docs, or the whole tile as coalesced 16-byte loads (a sparse
-      // tile's loads touch at most `tot` lines; the dense read is 2048 * VB bytes = 16 * VB lines of 128 B)
-      const int vb = (vtype == PA_INT || vtype == PA_FLOAT) ? 4 : 8;
-      if (tot <= (uint32_t)(6 * vb)) {
-        const int64_t d0 = doc_base + 32 * lane;
-        if (vb == 4) {
-          const AS1 uint32_t* rp = gp((const uint32_t*)raw) + d0;
-          lane_sparse(m, type, src, [&](int i) { return raw_bits(vtype, rp[i]); }, r0, r1);
-        } else {
-          const AS1 uint64_t* rp = gp((const uint64_t*)raw) + d0;
-          lane_sparse(m, type, src, [&](int i) { return rp[i]; }, r0, r1);
-        }
-      } else if (vb == 4) {
-        lane_raw_dense<4>((const char*)raw + doc_base * 4, m, lane, vtype, type, src, r0, r1);
-      } else {
-        lane_raw_dense<8>((const char*)raw + doc_base * 8, m, lane, vtype, type, src, r0, r1);
-      }
-      break;
-    }
-    if (STRAT == STRAT_LANE_RAW) break;  // (the raw kernel's columns are all raw: handled above)
-    if constexpr (STRAT == STRAT_LANE_DICT) {
-      if (type == PA_AGG_SUM && q->aggs[a].hist_card > 0) {
-        // shared dictionary: count the dictIds in the workgroup's LDS histogram (the values come in at the end)
-        lds_u32_t* hist = lds_ptr(lds + q->aggs[a].hist_off);
-        lane_sparse_hist(m, [&](int i) -> uint32_t {
-          return loff >= 0 ? decode_lds(img + loff, 32 * lane + i, nb) : decode_global(words, doc_base + 32 * lane + i, nb);
-        }, hist);
-        break;
-      }
-      // dictionary kernel: every tile walks the lanes' set bits (a lane's matching docs one after another, the wave
-      // max-popcount times): decode from the staged image (or HBM when lazy), then MIN / MAX of a sorted dictionary on
-      // the dictIds, anything else on the gathered values. One path (no per-width unpack calls): nothing spills.
-      auto dec = [&](int i) -> uint32_t {
-        return loff >= 0 ? decode_lds(img + loff, 32 * lane + i, nb) : decode_global(words, doc_base + 32 * lane + i, nb);
-      };
-      if (type != PA_AGG_SUM && (cs->cols[slot].flags & COLF_DICT_SORTED)) {
-        lane_sparse_ids(m, type == PA_AGG_MIN, dec, rid);
-        la.idm |= 1u << a;
-      } else {
-        lane_sparse(m, type, src, [&](int i) { return gp(dict)[dec(i)]; }, r0, r1);
-      }
-      break;
-    }
-    if (LM && kind == COL_SV_DICT && mx <= 12 &&
-        !(type != PA_AGG_SUM && (cs->cols[slot].flags & COLF_DICT_SORTED) && loff >= 0)) {
-      // dictionary column, few matching docs per lane: decode only those (staged image or HBM) and gather their values
-      if (loff >= 0) {
-        const uint32_t* region = img + loff;
-        lane_sparse(m, type, src, [&](int i) { return gp(dict)[decode_lds(region, 32 * lane + i, nb)]; }, r0, r1);
-      } else {
-        const int64_t d0 = doc_base + 32 * lane;
-        lane_sparse(m, type, src, [&](int i) { return gp(dict)[decode_global(words, d0 + i, nb)]; }, r0, r1);
-      }
-      break;
-    }
-    if (LM && kind == COL_SV_DICT && loff >= 0 &&
-        (type == PA_AGG_SUM || (cs->cols[slot].flags & COLF_DICT_SORTED))) {
-      const int mode = type == PA_AGG_SUM ? (src == SRC_INT ? LM_SUM_INT : (src == SRC_LONG ? LM_SUM_LONG : LM_SUM_DOUBLE))
-                                          : (type == PA_AGG_MIN ? LM_MIN_ID : LM_MAX_ID);
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-          (void*)dict, (short)0, cs->cols[slot].card * 8, 0x00020000);
-      lane_agg_lm_any(nb, lds_addr(img + loff), lane, m, mode, rs, r0, r1, rid);
-      if (mode >= LM_MIN_ID) la.idm |= 1u << a;
-      break;
-    }
-#pragma unroll 1
-    for (int h = 0; h < STEPS; h += kB) {
-      if (__ballot(((m >> h) & 0xffu) != 0) == 0) continue;
-      uint64_t v[kB];
-      if (kind == COL_SV_DICT) {
-        uint32_t id[kB];
-        decode_batch<kB, LM>(loff, nb, words, img, doc_base, h, m, lane, id);
-#pragma unroll
-        for (int i = 0; i < kB; ++i) v[i] = ((m >> (h + i)) & 1u) ? gp(dict)[id[i]] : 0ull;
-      } else if (vtype == PA_INT) {
-#pragma unroll
-        for (int i = 0; i < kB; ++i)
-          v[i] = ((m >> (h + i)) & 1u) ? (uint64_t)(int64_t)gp((const int32_t*)raw)[doc_base + local(h + i)] : 0ull;
-      } else if (vtype == PA_FLOAT) {
-#pragma unroll
-        for (int i = 0; i < kB; ++i)
-          v[i] = ((m >> (h + i)) & 1u) ? __builtin_bit_cast(uint64_t, (double)gp((const float*)raw)[doc_base + local(h + i)])
-                                      : 0ull;
-      } else {  // LONG, DOUBLE bits
-#pragma unroll
-        for (int i = 0; i < kB; ++i)
-          v[i] = ((m >> (h + i)) & 1u) ? gp((const uint64_t*)raw)[doc_base + local(h + i)] : 0ull;
-      }
-      if (type == PA_AGG_SUM) {
-        if (src == SRC_INT) {
-#pragma unroll
-          for (int i = 0; i < kB; ++i) r0 += (int64_t)v[i];
-        } else if (src == SRC_LONG) {
-#pragma unroll
-          for (int i = 0; i < kB; ++i) {
-            r0 += (int64_t)(uint32_t)v[i];
-            r1 += (int64_t)v[i] >> 32;
-          }
-        } else {
-          double d = __builtin_bit_cast(double, r0);
-#pragma unroll
-          for (int i = 0; i < kB; ++i) d += __builtin_bit_cast(double, v[i]);  // (0.0 for the docs that do not match)
-          r0 = __builtin_bit_cast(int64_t, d);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < kB; ++i) {
-          if (!((m >> (h + i)) & 1u)) continue;
-          const int64_t e = src == SRC_DOUBLE ? f64_order_encode(__builtin_bit_cast(double, v[i])) : (int64_t)v[i];
-          r0 = type == PA_AGG_MIN ? (e < r0 ? e : r0) : (e > r0 ? e : r0);
-        }
-      }
-    }
-    } while (false);
-    la_set(la, a, r0, r1);
-    la_set_rid(la, a, rid);
-  }
-}
-
-// End of the kernel: one wave reduction per accumulator and one device-scope atomic per wave.
-__device__ __forceinline__ void lane_acc_flush(const DevQuery* __restrict__ q, const WaveState& la, int lane) {
-#pragma unroll
-  for (int a = 0; a < kLaneAggs; ++a) {
-    if (a >= q->num_aggs) break;
-    const DevAgg& A = q->aggs[a];
-    if (A.type == PA_AGG_COUNT) continue;
-    int64_t r0, r1;
-    la_get(la, a, r0, r1);
-    if (A.type == PA_AGG_SUM) {
-      if (A.src == SRC_DOUBLE) {
-        const double s = wave_sum_f64(__builtin_bit_cast(double, r0));
-        if (lane == 0) __hip_atomic_fetch_add(gp(A.acc_f64), s, RLX);
-      } else if (A.src == SRC_LONG) {
-        const int64_t lo = wave_sum_i64(r0), hi = wave_sum_i64(r1);
-        if (lane == 0) {
-          __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64), (unsigned long long)lo, RLX);
-          __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64) + 1, (unsigned long long)hi, RLX);
-        }
-      } else {
-        const int64_t s = wave_sum_i64(r0);
-        if (lane == 0) __hip_atomic_fetch_add(gp((unsigned long long*)A.acc_i64), (unsigned long long)s, RLX);
-      }
-    } else if (A.type == PA_AGG_MIN) {
-      const int64_t r = wave_min_i64(r0);
-      if (lane == 0 && r != INT64_MAX) __hip_atomic_fetch_min(gp((long long*)A.acc_i64), (long long)r, RLX);
-    } else {
-      const int64_t r = wave_max_i64(r0);
-      if (lane == 0 && r != INT64_MIN) __hip_atomic_fetch_max(gp((long long*)A.acc_i64), (long long)r, RLX);
-    }
-  }
-}
-
-// STRAT_LANE_DICT, start of the kernel: the dictId histograms of SUMs over a shared dictionary to zero.
+                                              WaveState& la, unsigned char* lds);
+__device__ __forceinline__ void lane_acc_flush(const DevQuery* __restrict__ q, const WaveState& la, int lane);
 template <int WGS>
-__device__ __forceinline__ void lane_hist_zero(const DevQuery* q, unsigned char* lds_acc) {
-  for (int a = 0; a < q->num_aggs; ++a) {
-    const int hc = q->aggs[a].hist_card;
-    if (hc <= 0) continue;
-    uint32_t* h = (uint32_t*)(lds_acc + q->aggs[a].hist_off);
-    for (int i = threadIdx.x; i < hc; i += WGS) h[i] = 0u;
-  }
-  __syncthreads();
-}
-
-// STRAT_LANE_DICT, end of the kernel, before lane_acc_flush.
+__device__ __forceinline__ void lane_hist_zero(const DevQuery* q, unsigned char* lds_acc);
 template <int WGS>
 __device__ __forceinline__ void lane_hist_fold(const DevQuery* q, const DevSeg* segs, unsigned char* lds_acc,
-                                               const WaveState& la) {
-  // each thread folds histogram entries t, t + WGS, ... : count * value into its lane accumulator (exact split
-  // pair for 64-bit values: count < 2^32, so count * low32 and count * high32 fit their int64 halves)
-  __syncthreads();
-  for (int a = 0; a < q->num_aggs; ++a) {
-    const DevAgg& A = q->aggs[a];
-    if (A.hist_card <= 0) continue;
-    const uint32_t* h = (const uint32_t*)(lds_acc + A.hist_off);
-    const DevCol& c = segs[0].cols[A.slot];
-    int64_t r0, r1;
-    la_get(la, a, r0, r1);
-    for (int i = threadIdx.x; i < A.hist_card; i += WGS) {
-      const uint32_t n = h[i];
-      if (n == 0) continue;
-      if (A.src == SRC_DOUBLE) {
-        r0 = __builtin_bit_cast(int64_t, __builtin_bit_cast(double, r0) + (double)n * gp(c.dict_f64)[i]);
-      } else {
-        const int64_t v = gp(c.dict_i64)[i];
-        if (A.src == SRC_INT) {
-          r0 += (int64_t)n * v;
-        } else {
-          r0 += (int64_t)n * (int64_t)(uint32_t)v;
-          r1 += (int64_t)n * (v >> 32);
-        }
-      }
-    }
-    la_set(la, a, r0, r1);
-  }
-}
-
-// ---------------------------------------------------------------- selection (STRAT_SELECT)
-// SELECT ... ORDER BY ... LIMIT: the scan keeps, per wave, the candidates for the K smallest (key, row) entries of the
-// docs the filter kept (SelectionOrderByOperator.java:139-188: every matching doc offered to a bounded priority queue).
-// A wave owns a segment of CAP > K entries in an HBM scratch block and a private bound (its K-th smallest entry so far,
-// all ones at first): an entry below the bound is appended; a full segment is compacted in place to its K smallest
-// entries by a radix select over the 128-bit entries (linear, no sort), whose K-th becomes the bound. After a compaction
-// the wave publishes its K-th KEY to one global word (relaxed atomic min); every wave reads that word once per tile with
-// survivors and drops entries whose key exceeds it (inclusive: the row part is unknown; a stale read is only a looser
-// bound, so nothing is ordered). All candidate state is wave-private: no workgroup barrier in the tile loop (the waves
-// of a workgroup own tile ranges of different lengths). The finish kernels (pa_select.hip) select and sort the K
-// smallest of all waves' candidates.
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(4))) struct SelDesc CSel;
-typedef const __attribute__((address_space(4))) struct SelCol CSelCol;
-
-__device__ __forceinline__ bool sel_less(uint64_t ak, uint64_t ar, uint64_t bk, uint64_t br) {
-  return ak < bk || (ak == bk && ar < br);
-}
-__device__ __forceinline__ u64x2 sel_load(const SelEnt* e, uint64_t i) { return ((const AS1 u64x2*)e)[i]; }
-__device__ __forceinline__ void sel_store(SelEnt* e, uint64_t i, uint64_t key, uint64_t row) {
-  u64x2 v;
-  v.x = key;
-  v.y = row;
-  ((AS1 u64x2*)e)[i] = v;
-}
-
-// The threads of one radix select meet: a wave on its own (NT == 64: its LDS operations and its loads and stores are
-// ordered by the waits of the two fences; nothing else shares its state), or a workgroup of NT threads.
-template <int NT>
-__device__ __forceinline__ void sel_sync() {
-  if constexpr (NT == kWave) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  } else {
-    __syncthreads();
-  }
-}
-
-// The entry of 0-based `rank` in ascending order among the entries `each` enumerates (all distinct: rows are), found
-// byte by byte from the top: per byte, the entries that share the bytes found so far count their digit in st[0..256),
-// and the digit at which the running count passes the rank is the entry's. Bytes no entry uses (key_bits, row_bits)
-// are skipped. each(f) calls f(key, row) for this thread's share of the entries; st: kSelLdsWords LDS words.
-template <int NT, class Each>
-__device__ __forceinline__ void sel_threshold(Each each, uint32_t rank, int key_bits, int row_bits, lds_u32_t* st,
-                                              int tid, uint64_t& tk, uint64_t& tr) {
-  tk = 0;
-  tr = 0;
-  for (int p = 15; p >= 0; --p) {
-    const bool iskey = p >= 8;
-    const int sh = 8 * (p & 7);
-    if (sh >= (iskey ? key_bits : row_bits)) continue;
-    for (int b = tid; b < 256; b += NT) st[b] = 0u;
-    sel_sync<NT>();
-    const uint64_t ck = tk, cr = tr;
-    each([&](uint64_t k, uint64_t r) {
-      bool in;
-      uint32_t d;
-      if (iskey) {
-        in = sh == 56 || (k >> (sh + 8)) == (ck >> (sh + 8));
-        d = (uint32_t)(k >> sh) & 255u;
-      } else {
-        in = k == ck && (sh == 56 || (r >> (sh + 8)) == (cr >> (sh + 8)));
-        d = (uint32_t)(r >> sh) & 255u;
-      }
-      if (in) __hip_atomic_fetch_add(st + d, 1u, WG_RLX);
-    });
-    sel_sync<NT>();
-    if (tid < kWave) {  // (one wave: lane l holds digits 4l .. 4l + 3)
-      const uint32_t c0 = st[4 * tid], c1 = st[4 * tid + 1], c2 = st[4 * tid + 2], c3 = st[4 * tid + 3];
-      const uint32_t s = c0 + c1 + c2 + c3;
-      uint32_t incl = s;
-#pragma unroll
-      for (int o = 1; o < kWave; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o, kWave);
-        if (tid >= o) incl += t;
-      }
-      const uint32_t excl = incl - s;
-      if (rank >= excl && rank < incl) {
-        uint32_t r = rank - excl, d = 4u * (uint32_t)tid;
-        if (r >= c0) {
-          r -= c0;
-          ++d;
-          if (r >= c1) {
-            r -= c1;
-            ++d;
-            if (r >= c2) {
-              r -= c2;
-              ++d;
-            }
-          }
-        }
-        st[256] = d;
-        st[257] = r;
-      }
-    }
-    sel_sync<NT>();
-    const uint32_t d = st[256];
-    rank = st[257];
-    if (iskey) tk |= (uint64_t)d << sh;
-    else tr |= (uint64_t)d << sh;
-  }
-}
-
-// A wave's full candidate segment e[0..n) compacted in place to its K smallest entries (n > K), order kept; (tk, tr) =
-// the largest of them. Chunks of 64: every lane's entry of a chunk is loaded before any is stored (one load
-// instruction, waited for by the store's data), and a chunk's stores land at or below its own entries.
-__device__ __noinline__ u64x2 sel_compact(SelEnt* e, uint32_t n, uint32_t K, int key_bits, int row_bits, uint32_t st_lds,
-                                          int lane) {
-  lds_u32_t* st = (lds_u32_t*)(uintptr_t)st_lds;
-  uint64_t tk, tr;
-  auto each = [&](auto f) {
-    for (uint32_t i = (uint32_t)lane; i < n; i += kWave) {
-      const u64x2 v = sel_load(e, i);
-      f(v.x, v.y);
-    }
-  };
-  sel_threshold<kWave>(each, K - 1u, key_bits, row_bits, st, lane, tk, tr);
-  uint32_t w = 0;
-  for (uint32_t base = 0; base < n; base += kWave) {
-    const uint32_t i = base + (uint32_t)lane;
-    u64x2 v;
-    v.x = ~0ull;
-    v.y = ~0ull;
-    if (i < n) v = sel_load(e, i);
-    const bool keep = i < n && !sel_less(tk, tr, v.x, v.y);  // entry <= threshold
-    const uint64_t km = __ballot(keep);
-    const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(km >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km, 0u));
-    if (keep) sel_store(e, w + r, v.x, v.y);
-    w += (uint32_t)__builtin_popcountll(km);
-  }
-  sel_sync<kWave>();
-  u64x2 t;
-  t.x = tk;
-  t.y = tr;
-  return t;
-}
-
-// ORDER BY component j of one doc, in place in the key (DevQuery::sel: SelPart). Double.compare order for floating
-// values: every NaN the canonical one, then sign-magnitude bits mapped to unsigned order.
-__device__ __forceinline__ uint64_t sel_component(CSelCol* cp, int width, int shift, int desc, const uint32_t* img,
-                                                  int doc_local, int64_t doc) {
-  if (width == 0) return 0ull;  // a dictionary of one value
-  CSelCol& c = *cp;
-  uint64_t v;
-  if (c.kind == COL_SV_DICT) {
-    uint32_t id = c.lds_off >= 0 ? decode_lds(img + c.lds_off, doc_local, c.nbits) : decode_global(c.words, doc, c.nbits);
-    if (c.remap != nullptr) id = (uint32_t)gp(c.remap)[id];
-    v = id;
-  } else {
-    switch (c.vtype) {
-      case PA_INT: v = (uint32_t)gp((const int32_t*)c.raw)[doc] ^ 0x80000000u; break;
-      case PA_LONG: v = (uint64_t)gp((const int64_t*)c.raw)[doc] ^ 0x8000000000000000ull; break;
-      case PA_FLOAT: {
-        uint32_t b = gp((const uint32_t*)c.raw)[doc];
-        if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;
-        v = (b & 0x80000000u) ? (uint32_t)~b : (b | 0x80000000u);
-      } break;
-      default: {
-        uint64_t b = gp((const uint64_t*)c.raw)[doc];
-        if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) b = 0x7ff8000000000000ull;
-        v = (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-      } break;
-    }
-  }
-  if (desc) v = ~v & (width >= 64 ? ~0ull : ((1ull << width) - 1ull));
-  return v << shift;
-}
-
-// The docs of one tile that passed the filter (bit i of m: the lane's doc of step i) offered to the wave's candidates.
+                                               const WaveState& la);
+// pa_strat_select.h
 template <int STEPS, int LM>
 __device__ __forceinline__ void select_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
-                                            const uint32_t* img, int64_t doc_base, uint32_t m, int lane, WaveState& la) {
-  CSel* S = (CSel*)(uintptr_t)q->sel;
-  const int nob = S->nob;
-  const uint32_t K = (uint32_t)S->K, CAP = (uint32_t)S->cap;
-  CSelCol* cols = (CSelCol*)(uintptr_t)(S->ob_cols + (size_t)seg->index * nob);
-  SelEnt* e = S->scratch + (uint64_t)la.leap_slice * CAP;
-  const uint64_t gb = __hip_atomic_load(gp(S->bound), RLX);
-  const uint64_t seg_row = (uint64_t)(uint32_t)seg->index << 32;
-  for (int i = 0; i < STEPS; ++i) {
-    const bool act = ((m >> i) & 1u) != 0;
-    if (__ballot(act) == 0) continue;
-    const int dl = LM ? 32 * lane + i : i * kWave + lane;
-    const int64_t doc = doc_base + dl;
-    uint64_t key = 0;
-    if (act)
-      for (int j = 0; j < nob; ++j)
-        key |= sel_component(cols + j, S->part[j].width, S->part[j].shift, S->part[j].desc, img, dl, doc);
-    const uint64_t row = seg_row | (uint64_t)doc;
-    // strictly below the wave's bound (an all-ones key is still below the initial all-ones bound: its row is not)
-    bool pass = act && key <= gb && sel_less(key, row, la.sel_bk, la.sel_br);
-    for (;;) {
-      const uint64_t pm = __ballot(pass);
-      if (pm == 0) break;
-      const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(pm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm, 0u));
-      const uint32_t room = CAP - la.sel_n;
-      const bool take = pass && r < room;
-      if (take) sel_store(e, la.sel_n + r, key, row);
-      const uint32_t want = (uint32_t)__builtin_popcountll(pm);
-      const uint32_t tk = want < room ? want : room;
-      la.sel_n = (uint32_t)__builtin_amdgcn_readfirstlane((int)(la.sel_n + tk));
-      la.sel_app += tk;
-      pass = pass && !take;
-      if (la.sel_n == CAP) {
-        const u64x2 t = sel_compact(e, CAP, K, S->key_bits, S->row_bits, la.sel_lds, lane);
-        la.sel_n = K;
-        la.sel_bk = t.x;
-        la.sel_br = t.y;
-        ++la.sel_cmp;
-        if (lane == 0) __hip_atomic_fetch_min(gp(S->bound), (unsigned long long)t.x, RLX);
-        pass = pass && sel_less(key, row, t.x, t.y);
-      }
-    }
-  }
-}
-
-// Start of the kernel: no candidate yet, the bound all ones; the wave's select state in LDS.
-__device__ __forceinline__ void sel_state_init(WaveState& la, const uint32_t* smem, int wave) {
-  la.sel_n = la.sel_app = la.sel_cmp = 0u;
-  la.sel_bk = la.sel_br = ~0ull;
-  la.sel_lds = lds_addr(smem) + (uint32_t)wave * (uint32_t)(kSelLdsWords * 4);
-}
-
-// End of a segment run: the segment's matched docs (its share of numEntriesScannedPostFilter).
+                                            const uint32_t* img, int64_t doc_base, uint32_t m, int lane, WaveState& la);
+__device__ __forceinline__ void sel_state_init(WaveState& la, const uint32_t* smem, int wave);
 __device__ __forceinline__ void sel_segment_docs(const DevQuery* q, const DevSeg* seg, uint32_t matched,
-                                                 uint32_t matched_seg0, int lane) {
-  const int64_t sm = wave_sum_i64((int64_t)(matched - matched_seg0));
-  if (lane == 0 && sm != 0) __hip_atomic_fetch_add(gp(q->sel->seg_docs) + seg->index, (unsigned long long)sm, RLX);
-}
-
-// End of the kernel, every wave: the finish kernels read every wave's count.
-__device__ __forceinline__ void sel_counters_flush(const DevQuery* q, const WaveState& la, int lane) {
-  if (lane == 0) {
-    gp(q->sel->wave_n)[la.leap_slice] = la.sel_n;
-    if (la.sel_app) __hip_atomic_fetch_add(gp(q->sel->counters), (unsigned long long)la.sel_app, RLX);
-    if (la.sel_cmp) __hip_atomic_fetch_add(gp(q->sel->counters) + 1, (unsigned long long)la.sel_cmp, RLX);
-  }
-}
-
-// ---------------------------------------------------------------- distinct (STRAT_DISTINCT_LDS / STRAT_DISTINCT)
-// SELECT DISTINCT c1, c2, ...: the accumulator is a set of keys, one bit per key of the direct key space (bit key & 31
-// of word key >> 5, DevQuery::keybits; DistinctOperator.java:55-84 offers every matching doc's record to a set). Keys
-// are below 2^31 (kDistinctMaxKeys), so all key arithmetic is 32-bit.
-//   STRAT_DISTINCT_LDS: a workgroup-private bitmap in LDS in front of the tile rings, zeroed in the prologue; a matching
-//     doc is one no-return LDS OR; the epilogue ORs the non-zero words into the bitmap in HBM.
-//   STRAT_DISTINCT: the bitmap in HBM. A plain load of the key's word comes first and the relaxed OR is issued only
-//     when the bit is not yet set: a stale 0 costs a redundant atomic, and a 1 is never stale, because bits are only
-//     set between two resets. Batches of 8 steps: every key of the batch, then every word load, then the atomics, so
-//     one wait behind the ring's in-flight DMA (vmcnt counts in order) covers 8 loads per lane.
-// In both, when every active lane of a step has its key in one word (a hot key, a key range inside one word), the
-// lanes combine their bits and one of them updates (dst_combine); otherwise every lane updates on its own. Grouping the
-// lanes word by word, as accumulate_step groups equal keys, was measured and dropped: with a few lanes spread over a
-// few words per step it ran one ballot + shuffle pass per word and took 0.71 of 1.52 ms of the scan.
-// Measurement only (tuning debug_emit, results invalid; DESIGN section 5 takes the scan apart with them): bit 0 skips the
-// atomics, bit 1 also the global variant's word loads, bit 2 the in-wave combining (every lane goes on its own), bit 3
-// the global variant's word load only (a plain atomic per doc: no test-before-set).
-constexpr int kDstDbgNoAtomic = 1, kDstDbgNoLoad = 2, kDstDbgNoCombine = 4, kDstDbgPlainAtomic = 8;
-__device__ __forceinline__ uint32_t distinct_key(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
-                                                 const uint32_t* img, int doc_local, int64_t doc) {
-  uint32_t key = 0;
-  for (int j = 0; j < q->num_gb; ++j)
-    key += (uint32_t)gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc) * (uint32_t)q->gb_stride[j];
-  return key;
-}
-
-// One step's active lanes: true for the lanes that update the bitmap, with `bit` the OR of the bits of every lane they
-// stand for: the first active lane for all of them when they share one word, else every active lane for itself.
-__device__ __forceinline__ bool dst_combine(uint32_t word, uint32_t& bit, bool act, int lane) {
-  const uint64_t active = __ballot(act);
-  if (active == 0) return false;
-  const int leader = __builtin_ctzll(active);
-  const uint32_t w0 = (uint32_t)__shfl((int)word, leader);
-  if (__ballot(act && word == w0) != active) return act;
-  uint32_t b = act ? bit : 0u;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) b |= (uint32_t)__shfl_xor((int)b, o);
-  if (lane == leader) bit = b;
-  return lane == leader;
-}
-
-// The docs of one tile that passed the filter (bit i of m: the lane's doc of step i) into the bitmap.
+                                                 uint32_t matched_seg0, int lane);
+__device__ __forceinline__ void sel_counters_flush(const DevQuery* q, const WaveState& la, int lane);
+// pa_strat_distinct.h
 template <int STRAT, int STEPS, int LM>
 __device__ __forceinline__ void distinct_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                               const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
-                                              unsigned char* lds) {
-  auto local = [&](int i) { return LM ? 32 * lane + i : i * kWave + lane; };
-  const int dbg = q->debug_emit;
-  if constexpr (STRAT == STRAT_DISTINCT_LDS) {
-    lds_u32_t* bm = lds_ptr(lds);
-    for (int i = 0; i < STEPS; ++i) {
-      const bool act = ((m >> i) & 1u) != 0;
-      if (__ballot(act) == 0) continue;
-      const uint32_t key = act ? distinct_key(q, seg, img, local(i), doc_base + local(i)) : 0u;
-      uint32_t bit = 1u << (key & 31u);
-      const bool issue = (dbg & kDstDbgNoCombine) ? act : dst_combine(key >> 5, bit, act, lane);
-      if (dbg & kDstDbgNoAtomic) asm volatile("" ::"v"(bit), "v"(key));
-      else if (issue) __hip_atomic_fetch_or(bm + (key >> 5), bit, WG_RLX);
-    }
-  } else {
-    AS1 uint32_t* bm = gp(q->keybits);
-    constexpr int B = 8;
-    static_assert(STEPS % B == 0, "whole batches");
-    for (int i0 = 0; i0 < STEPS; i0 += B) {
-      const uint32_t mm = (m >> i0) & ((1u << B) - 1u);
-      if (__ballot(mm != 0) == 0) continue;
-      uint32_t word[B], bit[B], old[B];
-      uint32_t iss = 0;
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        const bool act = ((mm >> b) & 1u) != 0;
-        const uint32_t key = act ? distinct_key(q, seg, img, local(i0 + b), doc_base + local(i0 + b)) : 0u;
-        word[b] = key >> 5;
-        bit[b] = 1u << (key & 31u);
-      }
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        if (dbg & kDstDbgNoCombine) iss |= mm & (1u << b);
-        else if (__ballot((mm >> b) & 1u) != 0 && dst_combine(word[b], bit[b], ((mm >> b) & 1u) != 0, lane)) iss |= 1u << b;
-      }
-#pragma unroll
-      for (int b = 0; b < B; ++b)
-        old[b] = !((iss >> b) & 1u) ? ~0u : ((dbg & (kDstDbgNoLoad | kDstDbgPlainAtomic)) ? 0u : bm[word[b]]);
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        if (dbg & kDstDbgNoAtomic) asm volatile("" ::"v"(old[b]), "v"(bit[b]), "v"(word[b]));
-        else if ((bit[b] & ~old[b]) != 0) __hip_atomic_fetch_or(bm + word[b], bit[b], RLX);
-      }
-    }
-  }
-}
-
-// STRAT_DISTINCT_LDS, start of the kernel: the workgroup's bitmap to zero.
+                                              unsigned char* lds);
 template <int WGS>
-__device__ __forceinline__ void distinct_lds_zero(const DevQuery* q, unsigned char* lds) {
-  lds_u32_t* bm = lds_ptr(lds);
-  const uint32_t words = (uint32_t)((q->num_keys + 31) >> 5);
-  for (uint32_t w = threadIdx.x; w < words; w += WGS) bm[w] = 0u;
-  __syncthreads();
-}
-
-// STRAT_DISTINCT_LDS, end of the kernel: one global OR per non-zero word.
+__device__ __forceinline__ void distinct_lds_zero(const DevQuery* q, unsigned char* lds);
 template <int WGS>
-__device__ __forceinline__ void distinct_lds_flush(const DevQuery* q, unsigned char* lds) {
-  __syncthreads();
-  const lds_u32_t* bm = lds_ptr(lds);
-  const uint32_t words = (uint32_t)((q->num_keys + 31) >> 5);
-  for (uint32_t w = threadIdx.x; w < words; w += WGS) {
-    const uint32_t v = bm[w];
-    if (v != 0u) __hip_atomic_fetch_or(gp(q->keybits) + w, v, RLX);
-  }
-}
-
-// ---------------------------------------------------------------- filtered aggregations (STRAT_FILTERED_LDS / STRAT_FILTERED)
-// AGG(x) FILTER (WHERE F_j): the reference runs one filter + projection + executor per "swim lane"
-// (FilteredAggregationOperator.java:66-101, FilteredGroupByOperator.java:107-200: a walk over the segment per lane).
-// Here the columns stream once: after the query's own filter W left the tile's survivors m, every lane's CNF (FiltDesc)
-// gives m_j = m & F_j — literals on staged dictionary columns on the whole tile (leaf_bits), the others per surviving
-// doc (leaf_match_doc) — and the group key is computed once per doc of the lanes' union u (the shared group-key
-// generator, FilteredGroupByOperator.java:117-150: a group exists when any lane saw a doc of it; the group count
-// counts u). Lane j then accumulates its aggregations and its doc count (PA_ACC_LANE_COUNT_U64) under its own mask
-// with accumulate_step's wave pre-reduction; aggregations without a filter run under m (the main lane). Per segment
-// the docs of W and of every lane are counted by popcount (the execution statistics' input).
-//   STRAT_FILTERED_LDS: group counts, lane counts and every aggregation workgroup-private in LDS (the STRAT_LDS layout
-//     + u32 lane counts), flushed once per workgroup: one global atomic per cell of a lane that saw the key.
-//   STRAT_FILTERED: device-scope atomics per pre-reduced set.
-// Direct key spaces and single-value columns only (pa_query_prepare refuses the rest), step-major tiles.
-
-// Lane mask of one CNF (n literals, clause-major) over the tile's surviving docs m.
-template <int STEPS>
-__device__ __forceinline__ uint32_t filt_lane_mask(const DevLeaf* lits, int n, const uint32_t* img, int64_t doc_base,
-                                                   uint32_t m, int lane) {
-  uint32_t mj = m, clause = 0;
-  for (int li = 0; li < n; ++li) {
-    const DevLeaf& L = lits[li];
-    uint32_t bits = 0;
-    if ((L.kind == PA_LEAF_DICT_RANGE || L.kind == PA_LEAF_DICT_SET) && L.lds_off >= 0) {
-      bits = leaf_bits<STEPS>(L, img, doc_base, lane);
-    } else {
-      // not staged (or a raw column): only docs that can still change the lane's mask, each a doc of the segment
-      const uint32_t todo = mj & ~clause;
-      for (int i = 0; i < STEPS; ++i) {
-        if (__ballot((todo >> i) & 1u) == 0) continue;
-        if ((todo >> i) & 1u) bits |= (uint32_t)leaf_match_doc(L, doc_base + i * kWave + lane) << i;
-      }
-    }
-    clause |= bits;
-    if (L.clause_end) {
-      mj &= clause;
-      clause = 0;
-    }
-  }
-  return mj & m;  // (a negated leaf sets bits past the segment's last doc: process_tile)
-}
-
-// Lane j's mask out of the four pairs filtered_tile keeps (values, not references: a conditional between two lvalues
-// selects an address, and the masks would have to live in memory).
-__device__ __forceinline__ uint32_t filt_pair_mask(uint64_t p0, uint64_t p1, uint64_t p2, uint64_t p3, int j) {
-  const uint64_t k = (uint64_t)(j >> 1);
-  const uint64_t p = (p0 & (0ull - (uint64_t)(k == 0))) | (p1 & (0ull - (uint64_t)(k == 1))) |
-                     (p2 & (0ull - (uint64_t)(k == 2))) | (p3 & (0ull - (uint64_t)(k == 3)));
-  return (uint32_t)(p >> ((j & 1) * 32));
-}
-
-// One lane's docs of one 64-doc step (`set_mask`: wave mask) into the lane's doc count and aggregations: the equal-key
-// sets of accumulate_step. cell0 < 0: the count is the group's (Acc::add_count), else the lane count at cell0 + key.
-template <int STRAT>
-__device__ __forceinline__ void filtered_lane_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
-                                                   const uint32_t* img, int doc_local, int64_t doc, int64_t key,
-                                                   uint64_t set_mask, int lane, const Acc<STRAT>& acc,
-                                                   const int32_t* aggs, int naggs, int64_t cell0) {
-  uint64_t pending = set_mask;
-  bool first = true;
-  while (pending) {
-    const int leader = __builtin_ctzll(pending);
-    const int64_t k0 = __shfl(key, leader);
-    const uint64_t same = __ballot(key == k0) & pending;
-    const bool grouped = !first || (__builtin_popcountll(same) * 4 >= __builtin_popcountll(pending));
-    first = false;
-    const uint64_t set = grouped ? same : pending;
-    pending &= ~set;
-    const bool in = (set >> lane) & 1ull;
-    if (grouped) {
-      if (lane == leader) {
-        if (cell0 < 0) acc.add_count(k0, (uint32_t)__builtin_popcountll(set));
-        else acc.add_lane_count(cell0 + k0, (uint32_t)__builtin_popcountll(set));
-      }
-    } else if (in) {
-      if (cell0 < 0) acc.add_count(key, 1u);
-      else acc.add_lane_count(cell0 + key, 1u);
-    }
-    for (int x = 0; x < naggs; ++x) {
-      const int a = aggs[x];
-      agg_update_set<STRAT>(q->aggs[a], a, seg, img, doc_local, doc, key, k0, in, grouped, leader, lane, acc);
-    }
-  }
-}
-
-// The docs of one tile that passed W (bit i of m: the lane's doc of step i): lane masks, counters, aggregation.
+__device__ __forceinline__ void distinct_lds_flush(const DevQuery* q, unsigned char* lds);
+// pa_strat_filtered.h
 template <int STRAT, int STEPS>
 __device__ __forceinline__ void filtered_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                               const uint32_t* img, int64_t doc_base, uint32_t m, int lane,
-                                              const Acc<STRAT>& acc) {
-  const FiltDesc* __restrict__ F = uniform_ptr(q->filt);
-  const int NL = F->num_lanes;
-  const bool has_main = F->has_main != 0;
-  const DevLeaf* lits = uniform_ptr(F->leaves + (int64_t)seg->index * F->num_lits);
-  // the lanes' masks, two to a 64-bit scalar (lane j: bits 32 (j & 1) .. of pair j >> 1). Named scalars, not an array:
-  // an array indexed by the lane number stays in scratch memory, whose loads and stores wait behind the DMA ring.
-  static_assert(PA_MAX_AGG_FILTERS == 8 && STEPS <= 32, "four pairs of 32-bit lane masks");
-  uint64_t p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-  uint32_t u = has_main ? m : 0u;
-  for (int j = 0; j < NL; ++j) {
-    const int b = F->lit_begin[j];
-    const uint32_t mj = filt_lane_mask<STEPS>(lits + b, F->lit_begin[j + 1] - b, img, doc_base, m, lane);
-    const uint64_t w = (uint64_t)mj << ((j & 1) * 32);
-    p0 |= (j >> 1) == 0 ? w : 0ull;
-    p1 |= (j >> 1) == 1 ? w : 0ull;
-    p2 |= (j >> 1) == 2 ? w : 0ull;
-    p3 |= (j >> 1) == 3 ? w : 0ull;
-    u |= mj;
-  }
-  AS1 unsigned long long* sd = gp(F->seg_docs) + (int64_t)seg->index * (NL + 1);
-  {
-    const int64_t w = wave_sum_i64((int64_t)__builtin_popcount(m));
-    if (lane == 0 && w != 0) __hip_atomic_fetch_add(sd, (unsigned long long)w, RLX);
-  }
-  for (int j = 0; j < NL; ++j) {
-    const int64_t c = wave_sum_i64((int64_t)__builtin_popcount(filt_pair_mask(p0, p1, p2, p3, j)));
-    if (lane == 0 && c != 0) __hip_atomic_fetch_add(sd + 1 + j, (unsigned long long)c, RLX);
-  }
-  if (__ballot(u != 0) == 0) return;
-  const int64_t K = q->num_keys;
-  for (int i = 0; i < STEPS; ++i) {
-    const uint64_t um = __ballot((u >> i) & 1u);
-    if (um == 0) continue;
-    const int doc_local = i * kWave + lane;
-    const int64_t doc = doc_base + doc_local;
-    int64_t key = 0;
-    if ((um >> lane) & 1ull)
-      for (int j = 0; j < q->num_gb; ++j)
-        key += (int64_t)(gb_component(seg->cols[q->gb_slot[j]], seg->remap[j], img, doc_local, doc) *
-                         (uint64_t)q->gb_stride[j]);
-    // the group count under the union, with the main lane's aggregations when there is one (then u == m)
-    filtered_lane_step<STRAT>(q, seg, img, doc_local, doc, key, um, lane, acc, F->lane_aggs[NL],
-                              has_main ? F->lane_naggs[NL] : 0, -1);
-    for (int j = 0; j < NL; ++j) {
-      const uint64_t jm = __ballot((filt_pair_mask(p0, p1, p2, p3, j) >> i) & 1u);
-      if (jm == 0) continue;
-      filtered_lane_step<STRAT>(q, seg, img, doc_local, doc, key, jm, lane, acc, F->lane_aggs[j], F->lane_naggs[j],
-                                (int64_t)j * K);
-    }
-  }
-}
-
-// STRAT_FILTERED_LDS, start of the kernel: the workgroup's lane counts to zero, then the STRAT_LDS accumulators.
+                                              const Acc<STRAT>& acc);
 template <int WGS>
-__device__ __forceinline__ void filtered_lds_zero(const DevQuery* q, unsigned char* lds_acc) {
-  const FiltDesc* F = q->filt;
-  uint32_t* lc = (uint32_t*)(lds_acc + F->lds_lane_count_off);
-  const int64_t n = (int64_t)F->num_lanes * q->num_keys;
-  for (int64_t k = threadIdx.x; k < n; k += WGS) lc[k] = 0u;
-  lds_acc_zero<WGS>(q, lds_acc);
-}
-
-// STRAT_FILTERED_LDS, end of the kernel: for every key the workgroup saw, the group count, and for every lane that saw
-// it the lane count and that lane's aggregations (the cells of the other lanes hold identities: nothing to send).
+__device__ __forceinline__ void filtered_lds_zero(const DevQuery* q, unsigned char* lds_acc);
 template <int WGS>
-__device__ __forceinline__ void filtered_lds_flush(const DevQuery* q, unsigned char* lds_acc) {
-  __syncthreads();
-  const FiltDesc* F = q->filt;
-  const int64_t K = q->num_keys;
-  const int NL = F->num_lanes;
-  const uint32_t* cnt = (const uint32_t*)(lds_acc + q->lds_count_off);
-  const uint32_t* lc = (const uint32_t*)(lds_acc + F->lds_lane_count_off);
-  for (int64_t k = threadIdx.x; k < K; k += WGS) {
-    const uint32_t c = cnt[k];
-    if (c == 0) continue;
-    __hip_atomic_fetch_add(gp(q->count) + k, (unsigned long long)c, RLX);
-    for (int j = 0; j <= NL; ++j) {
-      if (j < NL) {
-        const uint32_t n = lc[(int64_t)j * K + k];
-        if (n == 0) continue;
-        __hip_atomic_fetch_add(gp(F->lane_count) + (int64_t)j * K + k, (unsigned long long)n, RLX);
-      } else if (!F->has_main) {
-        break;
-      }
-      for (int x = 0; x < F->lane_naggs[j]; ++x) lds_flush_agg(q->aggs[F->lane_aggs[j][x]], k, lds_acc);
-    }
-  }
-}
-
-// ---------------------------------------------------------------- expressions (STRAT_EXPR_LDS / STRAT_EXPR)
-// SUM(ADD(a, b)), GROUP BY timeConvert(ts, 'MILLISECONDS', 'DAYS'), ...: the reference puts a TransformOperator between
-// projection and executor (AggregationPlanNode / GroupByPlanNode), and the aggregation functions and
-// NoDictionary{Single,Multi}ColumnGroupKeyGenerator read its block values. Here a matching doc of a 64-doc step takes
-// two phases:
-//   gather    every distinct operand column of the query's expressions (ExprDesc::col_slot) is read once: first every
-//             dictionary column's dictId (staged image or HBM) and every raw column's value, then every dictionary
-//             gather — independent loads, issued back to back, so the step pays one HBM latency per phase, not one per
-//             operand. A value is kept as 64 bits in its family: int64 (INT / LONG) or double (FLOAT widened / DOUBLE).
-//   evaluate  the programs (ExprProg) run over eight 64-bit value registers. The program is wave-uniform and read with
-//             scalar loads, so the opcode dispatch is scalar control flow; the lanes differ only in their values.
-// Registers, column values and results are small arrays touched only with compile-time indices (a select chain per
-// access with the uniform runtime index: expr_get / expr_set), so they stay in VGPRs: no scratch memory, whose
-// accesses would wait behind the DMA ring.
-// A DOUBLE result aggregates as SRC_DOUBLE, a LONG result as SRC_LONG (agg_apply_set, the equal-key sets of
-// accumulate_step); a group-by expression contributes its 64 result bits (NaNs made one: doubleToLongBits) as a raw
-// LONG / DOUBLE column does, so such a query's key space is hashed.
-
-// Java's (long) cast of a double: NaN -> 0, saturating.
-__device__ __forceinline__ int64_t java_d2l(double d) {
-  if (d != d) return 0;
-  if (d >= 9223372036854775808.0) return INT64_MAX;
-  if (d <= -9223372036854775808.0) return INT64_MIN;
-  return (int64_t)d;
-}
-
-// TimeUnit.convert to a finer unit: d * m saturating at Long.MIN_VALUE / MAX_VALUE (m > 0).
-__device__ __forceinline__ int64_t tconv_mul(int64_t d, int64_t m) {
-  const int64_t over = INT64_MAX / m;
-  if (d > over) return INT64_MAX;
-  if (d < -over) return INT64_MIN;
-  return d * m;
-}
-
-// (expr_get / expr_set, the mask chains over the eight-element arrays: above accumulate_step, which reads the results)
-static_assert(PA_MAX_EXPR_REGS == PA_MAX_EXPR_COLUMNS && PA_MAX_EXPR_REGS == PA_MAX_EXPRS,
-              "expr_get / expr_set serve the registers, the column values and the results");
-
-// Gather phase: cv[c] = the doc's value of operand column c (int64, or a double's bits); bit c of the returned mask:
-// the column is FLOAT / DOUBLE in this segment (wave-uniform). Lanes outside `in` load nothing and hold zeros.
-__device__ __forceinline__ uint32_t expr_gather(const ExprDesc* __restrict__ E, const DevSeg* __restrict__ seg,
-                                                const uint32_t* img, int doc_local, int64_t doc, bool in,
-                                                uint64_t (&cv)[PA_MAX_EXPR_COLUMNS]) {
-  const int nc = E->num_cols;
-  uint32_t fmask = 0;
-  uint32_t id[PA_MAX_EXPR_COLUMNS];
-#pragma unroll
-  for (int c = 0; c < PA_MAX_EXPR_COLUMNS; ++c) {
-    cv[c] = 0;
-    id[c] = 0;
-    if (c >= nc) continue;
-    const DevCol& col = seg->cols[E->col_slot[c]];
-    if (col.vtype == PA_FLOAT || col.vtype == PA_DOUBLE) fmask |= 1u << c;
-    if (!in) continue;
-    if (col.kind == COL_SV_DICT) {
-      id[c] = decode_dict_id(col, img, doc_local, doc);
-    } else {
-      switch (col.vtype) {
-        case PA_INT: cv[c] = (uint64_t)(int64_t)gp((const int32_t*)col.raw)[doc]; break;
-        case PA_LONG: cv[c] = (uint64_t)gp((const int64_t*)col.raw)[doc]; break;
-        case PA_FLOAT: cv[c] = __builtin_bit_cast(uint64_t, (double)gp((const float*)col.raw)[doc]); break;
-        default: cv[c] = (uint64_t)gp((const int64_t*)col.raw)[doc]; break;
-      }
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < PA_MAX_EXPR_COLUMNS; ++c) {
-    if (c >= nc || !in) continue;
-    const DevCol& col = seg->cols[E->col_slot[c]];
-    if (col.kind != COL_SV_DICT) continue;
-    // (dict_i64 holds int64 values, dict_f64 doubles: 64 bits of the column's family either way)
-    cv[c] = ((fmask >> c) & 1u) ? (uint64_t)gp((const int64_t*)col.dict_f64)[id[c]] : (uint64_t)gp(col.dict_i64)[id[c]];
-  }
-  return fmask;
-}
-
-// Evaluate phase: one program over the gathered values; returns the result's 64 bits (a double's, or the int64).
-__device__ __forceinline__ uint64_t expr_eval(const ExprProg& P, const uint64_t (&cv)[PA_MAX_EXPR_COLUMNS],
-                                              uint32_t fmask) {
-  uint64_t r[PA_MAX_EXPR_REGS];
-#pragma unroll
-  for (int k = 0; k < PA_MAX_EXPR_REGS; ++k) r[k] = 0;
-  uint64_t last = 0;
-  const int n = P.num_ops;
-  for (int o = 0; o < n; ++o) {
-    const ExprOp& X = P.ops[o];
-    const int op = X.op;
-    uint64_t out;
-    if (op == PA_EXPR_LOAD_COL) {
-      const uint64_t x = expr_get(cv, X.a);
-      const bool fl = (fmask >> X.a) & 1u;
-      if (X.b == PA_EXPR_DOUBLE)
-        out = fl ? x : __builtin_bit_cast(uint64_t, (double)(int64_t)x);
-      else
-        out = fl ? (uint64_t)java_d2l(__builtin_bit_cast(double, x)) : x;
-    } else {
-      const uint64_t ab = X.a_kind == PA_EXPR_ARG_REG ? expr_get(r, X.a) : (uint64_t)X.a_imm;
-      if (op <= PA_EXPR_MOD) {
-        const uint64_t bb = X.b_kind == PA_EXPR_ARG_REG ? expr_get(r, X.b) : (uint64_t)X.b_imm;
-        const double a = __builtin_bit_cast(double, ab), b = __builtin_bit_cast(double, bb);
-        double d;
-        if (op == PA_EXPR_ADD) d = a + b;
-        else if (op == PA_EXPR_SUB) d = a - b;
-        else if (op == PA_EXPR_MUL) d = a * b;
-        else if (op == PA_EXPR_DIV) d = a / b;
-        else d = fmod(a, b);
-        out = __builtin_bit_cast(uint64_t, d);
-      } else if (op == PA_EXPR_ABS) {
-        out = ab & 0x7fffffffffffffffull;
-      } else if (op == PA_EXPR_CEIL) {
-        out = __builtin_bit_cast(uint64_t, ceil(__builtin_bit_cast(double, ab)));
-      } else if (op == PA_EXPR_FLOOR) {
-        out = __builtin_bit_cast(uint64_t, floor(__builtin_bit_cast(double, ab)));
-      } else if (op == PA_EXPR_D2L) {
-        out = (uint64_t)java_d2l(__builtin_bit_cast(double, ab));
-      } else if (op == PA_EXPR_L2D) {
-        out = __builtin_bit_cast(uint64_t, (double)(int64_t)ab);
-      } else if (op == PA_EXPR_TCONV_DIV) {
-        out = (uint64_t)((int64_t)ab / X.b_imm);
-      } else {
-        out = (uint64_t)tconv_mul((int64_t)ab, X.b_imm);
-      }
-    }
-    expr_set(r, X.dst, out);
-    last = out;
-  }
-  return last;
-}
-
-// One 64-doc step of a query with expressions: gather, evaluate every program, then accumulate_step with the results.
+__device__ __forceinline__ void filtered_lds_flush(const DevQuery* q, unsigned char* lds_acc);
+// pa_strat_expr.h
 template <int STRAT>
 __device__ __forceinline__ void expr_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                           const uint32_t* img, int doc_local, int64_t doc, uint64_t matched, int lane,
-                                          const Acc<STRAT>& acc) {
-  ExprVals ev;
-  ev.E = uniform_ptr(q->expr);
-  const bool mine = (matched >> lane) & 1ull;
-  uint64_t cv[PA_MAX_EXPR_COLUMNS];
-  const uint32_t fmask = expr_gather(ev.E, seg, img, doc_local, doc, mine, cv);
-  const int ne = ev.E->num_exprs;
-#pragma unroll
-  for (int e = 0; e < PA_MAX_EXPRS; ++e) ev.res[e] = 0;
-  for (int e = 0; e < ne; ++e) {  // (not unrolled: one copy of the evaluator in the kernel)
-    uint64_t x = expr_eval(ev.E->progs[e], cv, fmask);
-    // (one NaN: doubleToLongBits, for the group key; SUM / MIN / MAX treat every NaN alike)
-    if (ev.E->progs[e].result_type == PA_EXPR_DOUBLE && (x & 0x7fffffffffffffffull) > 0x7ff0000000000000ull)
-      x = 0x7ff8000000000000ull;
-    expr_set(ev.res, e, x);
-  }
-  accumulate_step<STRAT>(q, seg, img, doc_local, doc, matched, lane, acc, &ev);
-}
+                                          const Acc<STRAT>& acc);
 
 // The rare part of a tile (some doc survived the eager clauses): lazy clauses per surviving doc, then aggregation.
 // Returns the docs that matched.

@@ -1,6 +1,6 @@
-// Scan-kernel variants of the distinct strategies (SELECT DISTINCT ...: pa_scan.h "distinct"): the LDS bitmap and the
+// Scan-kernel variants of the distinct strategies (SELECT DISTINCT ...: pa_strat_distinct.h "distinct"): the LDS bitmap and the
 // global bitmap, step-major tiles of 2048 or 1024 docs.
-#include "pa_scan.h"
+#include "pa_strat_distinct.h"
 
 namespace pa {
 

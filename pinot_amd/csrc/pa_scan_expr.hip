@@ -1,6 +1,7 @@
-// Scan-kernel variants of the transform-expression strategies (SUM(ADD(a, b)), GROUP BY timeConvert(...): pa_scan.h
-// "expressions"): workgroup-private LDS accumulators and device-scope atomics, step-major tiles of 2048 or 1024 docs.
-#include "pa_scan.h"
+// Scan-kernel variants of the transform-expression strategies (SUM(ADD(a, b)), GROUP BY timeConvert(...):
+// pa_strat_expr.h "expressions"): workgroup-private LDS accumulators and device-scope atomics, step-major tiles of 2048
+// or 1024 docs.
+#include "pa_strat_expr.h"
 
 namespace pa {
 

@@ -1,6 +1,7 @@
-// Scan-kernel variants of the filtered-aggregation strategies (AGG(x) FILTER (WHERE ...): pa_scan.h "filtered
-// aggregations"): workgroup-private LDS accumulators and device-scope atomics, step-major tiles of 2048 or 1024 docs.
-#include "pa_scan.h"
+// Scan-kernel variants of the filtered-aggregation strategies (AGG(x) FILTER (WHERE ...): pa_strat_filtered.h
+// "filtered aggregations"): workgroup-private LDS accumulators and device-scope atomics, step-major tiles of 2048 or 1024
+// docs.
+#include "pa_strat_filtered.h"
 
 namespace pa {
 

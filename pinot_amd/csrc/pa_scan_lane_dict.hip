@@ -1,6 +1,6 @@
 // Scan-kernel variant of aggregation-only queries over dictionary columns only (STRAT_LANE_DICT):
 // lane-major.
-#include "pa_scan.h"
+#include "pa_strat_lane.h"
 
 namespace pa {
 

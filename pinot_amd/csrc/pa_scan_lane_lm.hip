@@ -1,7 +1,7 @@
 // Scan-kernel variants of aggregation-only queries, lane-major tiles: STRAT_LANE and the COUNT-only
 // STRAT_LANE_CNT. The other single-kind variants, lane-major only like _CNT, compile for minutes each and have units of
 // their own (pa_scan_lane_raw.hip, pa_scan_lane_dict.hip).
-#include "pa_scan.h"
+#include "pa_strat_lane.h"
 
 namespace pa {
 

@@ -1,5 +1,5 @@
 // Scan-kernel variant of aggregation-only queries over raw columns only (STRAT_LANE_RAW): lane-major.
-#include "pa_scan.h"
+#include "pa_strat_lane.h"
 
 namespace pa {
 

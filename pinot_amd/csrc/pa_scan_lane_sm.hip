@@ -1,5 +1,5 @@
 // Scan-kernel variants of aggregation-only queries, step-major tiles of 2048 or 1024 docs: STRAT_LANE.
-#include "pa_scan.h"
+#include "pa_strat_lane.h"
 
 namespace pa {
 

@@ -1,6 +1,6 @@
-// Scan-kernel variants of the selection strategy (SELECT ... ORDER BY ... LIMIT: pa_scan.h "selection"): step-major
+// Scan-kernel variants of the selection strategy (SELECT ... ORDER BY ... LIMIT: pa_strat_select.h "selection"): step-major
 // tiles of 2048 or 1024 docs.
-#include "pa_scan.h"
+#include "pa_strat_select.h"
 
 namespace pa {
 

@@ -1,11 +1,11 @@
-// Selection queries (SELECT columns ... ORDER BY ... LIMIT), everything but the scan strategy itself (pa_scan.h
-// "selection", pa_scan_select.hip): the C-ABI entry points, the planner's part, and the finish kernels that turn the
-// scan waves' candidates into the result — gather the candidates the final bound admits, select the K smallest (the
-// same radix select the waves compact with, one workgroup), sort them (bitonic, in global memory: K <= 65536), decode
-// the output cells. Reference: SelectionOrderByOperator.java:193-322 (the queue drained into rows, the non-ordered
+// Selection queries (SELECT columns ... ORDER BY ... LIMIT), everything but the scan strategy itself
+// (pa_strat_select.h "selection", pa_scan_select.hip): the C-ABI entry points, the planner's part, and the finish
+// kernels that turn the scan waves' candidates into the result — gather the candidates the final bound admits, select
+// the K smallest (the same radix select the waves compact with, one workgroup), sort them (bitonic, in global memory:
+// K <= 65536), decode the output cells. Reference: SelectionOrderByOperator.java:193-322 (the queue drained into rows, the non-ordered
 // columns fetched for the kept docs only) and SelectionOrderByCombineOperator (the segments' queues merged).
 #include "pa_host.h"
-#include "pa_scan.h"
+#include "pa_strat_select.h"
 
 namespace pa {
 

@@ -1,6 +1,6 @@
 """Aggregation-only queries on the per-lane register path (STRAT_LANE, lane-major tiles) against the oracle.
 
-The path picks, per tile and aggregation (pa_scan.h lane_acc_tile):
+The path picks, per tile and aggregation (pa_strat_lane.h lane_acc_tile):
   raw columns        sparse tiles: per-doc loads of the matching docs; dense tiles: the whole tile as coalesced 16-byte
                      loads with every value's match bit fetched from the lane that owns its doc (ds_bpermute)
   dictionary columns few matches per lane: decode + gather of those docs only; else the static-unpack full-tile path

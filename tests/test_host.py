@@ -86,6 +86,23 @@ def test_build_covers_every_source_and_rebuilds_objects_by_includes(monkeypatch)
     assert len(scan_units) >= 11
     for s in scan_units:  # every unit that instantiates scan kernels
         assert "pa_scan.h" in deps[s] and "pa_host.h" not in deps[s], s
+    # strategies in headers of their own (pa_strat_*.h): no other header of csrc/ reaches one, nor does a unit of another
+    # strategy, the dense kernel's unit or pa_kernels.hip; each reaches exactly its own units
+    headers = [h for h in os.listdir(B.CSRC) if h.endswith(".h")]
+    hdeps = {h: {os.path.basename(d) for d in B._deps(os.path.join(B.CSRC, h))} - {h} for h in headers}
+    strats = {h for h in headers if h.startswith("pa_strat_")}
+    assert strats >= {"pa_strat_%s.h" % n for n in ("lane", "select", "distinct", "filtered", "expr")}
+    for h in headers:
+        assert not hdeps[h] & strats, h
+    assert not (deps["pa_scan_gdense.hip"] | deps["pa_kernels.hip"] | deps["pa_scan_std.hip"]) & strats
+    own = {"pa_strat_select.h": ["pa_select.hip"], "pa_strat_distinct.h": ["pa_distinct.hip"]}
+    units_of = {h: sorted([s for s in scan_units if s.startswith("pa_scan_" + h[len("pa_strat_"):-2])] + own.get(h, []))
+                for h in strats}
+    assert len(units_of["pa_strat_lane.h"]) == 4 and units_of["pa_strat_expr.h"] == ["pa_scan_expr.hip"]
+    for h in strats:
+        assert sorted(s for s in B.SOURCES if h in deps[s]) == units_of[h], h
+    part_units = [s for s in scan_units if s.startswith("pa_scan_part_")]
+    assert len(part_units) == 3 and not any(deps[s] & (strats - {"pa_strat_part.h"}) for s in part_units)
     t0 = 1_000_000.0
     real_exists = os.path.exists
 
@@ -98,3 +115,7 @@ def test_build_covers_every_source_and_rebuilds_objects_by_includes(monkeypatch)
     assert stale == {s for s in B.SOURCES if "pa_host.h" in deps[s]} and "pa_scan_std.hip" not in stale
     monkeypatch.setattr(os.path, "getmtime", mtime("pa_plan.hip"))
     assert B._stale_objs() == ["pa_plan.hip"]
+    # an edit to one strategy header rebuilds that strategy's units only
+    for h in sorted(strats):
+        monkeypatch.setattr(os.path, "getmtime", mtime(h))
+        assert sorted(B._stale_objs()) == units_of[h], h

@@ -385,7 +385,7 @@ def run_distinct(nseg, docs, reps, warm=0, tuning=None):
     groups = (
         (lambda i: B.make_segment(100 + i, docs), (
             ("a_distinct_days", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where, None),
-            # the scan taken apart (tuning debug_emit, results invalid: pa_scan.h "distinct"): without the in-wave
+            # the scan taken apart (tuning debug_emit, results invalid: pa_strat_distinct.h "distinct"): without the in-wave
             # combining, without the LDS atomics, without both; and the global variant on the same query
             ("a_distinct_days_no_combine", "SELECT DISTINCT daysSinceEpoch FROM AdAnalyticsTable%s LIMIT 1000" % where,
              {"debug_emit": 4}),
