@@ -22,6 +22,7 @@ constexpr int kSteps = 32;                    // 64-doc steps per wave tile
 constexpr int kWTileDocs = kWave * kSteps;    // 2048 docs: one wave tile; 64*nb stream words per column
 constexpr int kMaxSlots = 12;                 // distinct columns referenced by one query
 constexpr int kGuardWords = 4;
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // one 16-byte load / store
 
 enum ColKind : int32_t { COL_NONE = 0, COL_SV_DICT = 1, COL_SV_RAW = 2, COL_MV_DICT = 3 };
 // Partitioned aggregation (high-cardinality dense GROUP BY), three kernels over the same tile -> wave schedule:

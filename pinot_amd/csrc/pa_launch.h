@@ -1,5 +1,5 @@
-// Host-callable launchers of the kernel units (pa_kernels.hip, pa_merge.hip, pa_stats.hip, pa_pve.hip) with their
-// descriptors.
+// Host-callable launchers of the kernel units (pa_kernels.hip, pa_prep.hip, pa_compact.hip, pa_launch_scan.hip,
+// pa_merge.hip, pa_stats.hip, pa_pve.hip) with their descriptors, and the kernel-pointer getters of the scan units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pa_device.h"
@@ -90,6 +90,13 @@ hipError_t launch_limit_passes(const DevQuery* q, const DevSeg* segs, const Limi
 constexpr int64_t kWalkMaxWords = 40000;  // LDS bitmap of at most 160000 bytes
 hipError_t launch_limit_walk(const DevQuery* q, const DevSeg* segs, int nseg, int64_t words, bool mv, bool use_tab,
                              hipStream_t s);
+// blocks of `block` threads for n elements of a grid-stride kernel
+inline int grid_for(int64_t n, int block) {
+  int64_t g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > 4096) g = 4096;
+  return (int)g;
+}
 hipError_t launch_bswap_words(uint32_t* w, int64_t n, hipStream_t s);
 hipError_t launch_hll_lut_numeric(const int64_t* di, const double* dd, int32_t vtype, int32_t card, int32_t log2m,
                                   uint32_t* lut, hipStream_t s);
@@ -211,6 +218,22 @@ hipError_t launch_leapfrogs(const LfJob* jobs, int nj, int64_t lanes, hipStream_
 hipError_t launch_pve_lists(const uint32_t* hist, uint32_t* off, uint64_t* base, const uint32_t* table,
                             const uint32_t* used, uint32_t* index, uint32_t* tot, int G, int P, int64_t C, int cr,
                             hipStream_t s);
+// Kernel-pointer getters of the scan variants, one translation unit per group (parallel builds): nullptr when the
+// unit does not hold the strategy.
+const void* scan_fn_std(int strategy, int steps, int lm);        // pa_scan_std.hip: STRAT_LDS
+const void* scan_fn_global(int strategy, int steps, int lm);     // pa_scan_global.hip: STRAT_GLOBAL
+const void* scan_fn_lane_lm(int strategy, int steps, int lm);    // pa_scan_lane_lm.hip: STRAT_LANE, _CNT, lane-major
+const void* scan_fn_lane_raw(int strategy, int steps, int lm);   // pa_scan_lane_raw.hip: STRAT_LANE_RAW (lane-major)
+const void* scan_fn_lane_dict(int strategy, int steps, int lm);  // pa_scan_lane_dict.hip: STRAT_LANE_DICT (lane-major)
+const void* scan_fn_lane_sm(int strategy, int steps, int lm);    // pa_scan_lane_sm.hip: STRAT_LANE, step-major
+const void* scan_fn_part_a(int strategy);                  // pa_scan_part_a.hip: PCOUNT + emit variants (one part)
+const void* scan_fn_part_b(int strategy);                  // pa_scan_part_b.hip: the other emit variants
+const void* scan_fn_part_mv(int strategy);                 // pa_scan_part_mv.hip: the multi-value group-by passes
+const void* scan_fn_gdense(int strategy, int lm);          // pa_scan_gdense.hip: STRAT_GDENSE (pa_gdense.h)
+const void* scan_fn_select(int strategy, int steps);       // pa_scan_select.hip: STRAT_SELECT (step-major tiles)
+const void* scan_fn_distinct(int strategy, int steps);     // pa_scan_distinct.hip: STRAT_DISTINCT* (step-major tiles)
+const void* scan_fn_filtered(int strategy, int steps);     // pa_scan_filtered.hip: STRAT_FILTERED* (step-major tiles)
+const void* scan_fn_expr(int strategy, int steps);         // pa_scan_expr.hip: STRAT_EXPR* (step-major tiles)
 hipError_t set_scan_lds_limit(int strategy, int steps, int lm, int bytes);
 hipError_t scan_occupancy(int strategy, int steps, int lm, int lds_bytes, int* blocks_per_cu);
 hipError_t launch_scan(int strategy, int steps, int lm, int grid, int lds_bytes, const DevQuery* q, const DevSeg* segs,

@@ -1,5 +1,5 @@
 // Scan-kernel variants of the partitioned aggregation, part A: the count pass and the emit variants without an H stream.
-#include "pa_scan.h"
+#include "pa_strat_part.h"
 
 namespace pa {
 

@@ -1,5 +1,5 @@
 // Scan-kernel variants of the partitioned aggregation, part B: the emit variants with an H (DISTINCTCOUNTHLL) stream.
-#include "pa_scan.h"
+#include "pa_strat_part.h"
 
 namespace pa {
 

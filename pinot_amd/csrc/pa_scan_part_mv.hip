@@ -1,6 +1,6 @@
 // Explicit instantiations of the partitioned passes of a multi-value group-by (one V record per (doc, value) pair):
 // the count pass and the V-only emit variants (no generic records), in their own translation unit for parallel builds.
-#include "pa_scan.h"
+#include "pa_strat_part.h"
 
 namespace pa {
 

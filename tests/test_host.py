@@ -91,10 +91,13 @@ def test_build_covers_every_source_and_rebuilds_objects_by_includes(monkeypatch)
     headers = [h for h in os.listdir(B.CSRC) if h.endswith(".h")]
     hdeps = {h: {os.path.basename(d) for d in B._deps(os.path.join(B.CSRC, h))} - {h} for h in headers}
     strats = {h for h in headers if h.startswith("pa_strat_")}
-    assert strats >= {"pa_strat_%s.h" % n for n in ("lane", "select", "distinct", "filtered", "expr")}
+    assert strats >= {"pa_strat_%s.h" % n for n in ("lane", "select", "distinct", "filtered", "expr", "part")}
     for h in headers:
         assert not hdeps[h] & strats, h
     assert not (deps["pa_scan_gdense.hip"] | deps["pa_kernels.hip"] | deps["pa_scan_std.hip"]) & strats
+    # the kernel units that share no device code with the scan (and the scan's dispatch) do not reach its headers
+    for s in ("pa_compact.hip", "pa_prep.hip", "pa_launch_scan.hip"):
+        assert "pa_launch.h" in deps[s] and not deps[s] & ({"pa_scan.h", "pa_gdense.h"} | strats), s
     own = {"pa_strat_select.h": ["pa_select.hip"], "pa_strat_distinct.h": ["pa_distinct.hip"]}
     units_of = {h: sorted([s for s in scan_units if s.startswith("pa_scan_" + h[len("pa_strat_"):-2])] + own.get(h, []))
                 for h in strats}
@@ -103,6 +106,7 @@ def test_build_covers_every_source_and_rebuilds_objects_by_includes(monkeypatch)
         assert sorted(s for s in B.SOURCES if h in deps[s]) == units_of[h], h
     part_units = [s for s in scan_units if s.startswith("pa_scan_part_")]
     assert len(part_units) == 3 and not any(deps[s] & (strats - {"pa_strat_part.h"}) for s in part_units)
+    assert units_of["pa_strat_part.h"] == sorted(part_units)  # (the loops above and below so cover the partitioned header)
     t0 = 1_000_000.0
     real_exists = os.path.exists
 
@@ -119,3 +123,7 @@ def test_build_covers_every_source_and_rebuilds_objects_by_includes(monkeypatch)
     for h in sorted(strats):
         monkeypatch.setattr(os.path, "getmtime", mtime(h))
         assert sorted(B._stale_objs()) == units_of[h], h
+    # an edit to the scan's device code rebuilds the scan units, pa_kernels.hip and the two host units that include a
+    # strategy, and nothing else
+    monkeypatch.setattr(os.path, "getmtime", mtime("pa_scan.h"))
+    assert set(B._stale_objs()) == set(scan_units) | {"pa_kernels.hip", "pa_select.hip", "pa_distinct.hip"}
