@@ -375,7 +375,9 @@ __device__ __forceinline__ void lane_acc_tile(const DevQuery* __restrict__ q, co
       }
       break;
     }
-    if (LM && kind == COL_SV_DICT && loff >= 0 &&
+    // (lane_agg_lm's 32-bit byte offset id << 3 and the resource's card * 8 bytes hold for dictionaries below 2^28
+    // values; a larger one takes the generic gather below)
+    if (LM && kind == COL_SV_DICT && loff >= 0 && cs->cols[slot].card < (1 << 28) &&
         (type == PA_AGG_SUM || (cs->cols[slot].flags & COLF_DICT_SORTED))) {
       const int mode = type == PA_AGG_SUM ? (src == SRC_INT ? LM_SUM_INT : (src == SRC_LONG ? LM_SUM_LONG : LM_SUM_DOUBLE))
                                           : (type == PA_AGG_MIN ? LM_MIN_ID : LM_MAX_ID);
