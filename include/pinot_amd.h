@@ -40,6 +40,11 @@
  *      aggregate / aggregateGroupBySV / aggregateGroupByMV (every value into a DoubleArrayList) become per-group value
  *      histograms inside the scan, extractAggregationResult / extractGroupByResult the compacted (value id, count)
  *      pairs, extractFinalResult (sort + index at the percentile's rank) a rank select over the bins on the GPU.
+ *  pa_query_fetch_trimmed
+ *      replaces, for a direct key space, the server's group trim: data/table/IndexedTable.java:149 (finish) with
+ *      data/table/TableResizer.java:187-238 (resizeRecordsMap: the top `trim` records under the ORDER BY comparator) at
+ *      the capacity of GroupByUtils.getTableCapacity / operator/combine/GroupByCombineOperator.java:63-73 — an MSB
+ *      radix select over order words in HBM, then a gather of the kept groups' rows only.
  *  pa_query_set_selection / pa_query_bind_order_remap / pa_query_fetch_selection
  *      replace, for one segment set on one GPU, operator/query/SelectionOnlyOperator.java,
  *      operator/query/SelectionOrderByOperator.java:108-112 (the comparator), :139-188 (every ordered expression
@@ -583,6 +588,40 @@ void* pa_query_section(const pa_query* q, int32_t section, int32_t* kind, int64_
  * so a caller can size its arrays exactly before the real fetch. Synchronises `stream`. */
 int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out_keys,
                        int64_t* out_counts, void* const* out_aggs);
+
+/* pa_query_fetch with the server's group trim done on the GPU: of the n non-empty groups only the `trim` smallest under
+ * the ORDER BY comparator are gathered and copied, in ascending key order, into the same arrays as pa_query_fetch.
+ * Replaces, for a direct key space, IndexedTable.finish (IndexedTable.java:149) with TableResizer.resizeRecordsMap
+ * (TableResizer.java:187-238: the records' order-by values extracted, the top `trim` kept) at the capacity of
+ * GroupByUtils.getTableCapacity / GroupByCombineOperator.java:63-73 (the caller passes it as `trim`: max(5 * limit,
+ * minServerGroupTrimSize) under ORDER BY, else the limit).
+ * A term compares a group-by column's value (PA_TRIM_KEY_COLUMN: by table-wide id — the table dictionaries are sorted
+ * ascending), the group's count, or an aggregation's FINAL value as a double: a SUM / MIN / MAX exactly as pa_query_fetch
+ * returns it (a 96-bit SUM rounded once, so sums that round to one double tie), AVG = that sum / count and MINMAXRANGE
+ * = max - min in IEEE double; -0.0 ties with +0.0; `desc` reverses the term. Ties of all terms are broken by the group
+ * key ids, group-by column 0 most significant, ascending. num_terms = 0 keeps the `trim` smallest key tuples. NaN term
+ * values are out of scope: the comparator of the reference is no total order over them.
+ * PA_EUNSUPPORTED (the caller trims the full fetch on the host instead): a hashed key space (so any expression key), a
+ * query with a VALUE_HISTOGRAM aggregation or aggregation filters (their fetch calls follow the full fetch's group
+ * order), more than PA_MAX_TRIM_TERMS terms, a term over any other aggregation type (HLL, DISTINCTCOUNT, COUNT_MV).
+ * HLL / DISTINCTCOUNT aggregations that are only read are gathered for the kept groups.
+ * Returns min(n, trim) (may exceed capacity: then nothing was written; call again with that capacity), <0 on error;
+ * *out_total_groups = n. With n <= trim the call is pa_query_fetch. Fills pa_query_matched_docs and
+ * pa_query_num_groups_limit_reached as pa_query_fetch does. Synchronises `stream`. */
+#define PA_TRIM_KEY_COLUMN 0   /* index = group-by position */
+#define PA_TRIM_COUNT 1
+#define PA_TRIM_AGG 2          /* index = aggregation (SUM / MIN / MAX): its final double */
+#define PA_TRIM_AVG 3          /* index = SUM aggregation; value = sum / count */
+#define PA_TRIM_RANGE 4        /* index = MAX aggregation, index2 = MIN aggregation */
+#define PA_MAX_TRIM_TERMS 4
+typedef struct {
+  int32_t num_terms;
+  int32_t kind[PA_MAX_TRIM_TERMS], index[PA_MAX_TRIM_TERMS], index2[PA_MAX_TRIM_TERMS], desc[PA_MAX_TRIM_TERMS];
+  int64_t trim;
+} pa_trim_spec;
+int64_t pa_query_fetch_trimmed(pa_query* q, void* stream, const pa_trim_spec* spec, int64_t capacity,
+                               int64_t* out_keys, int64_t* out_counts, void* const* out_aggs,
+                               int64_t* out_total_groups);
 
 /* The bins of VALUE_HISTOGRAM aggregation `agg` for the groups pa_query_fetch returns for the current accumulators, in
  * the same order (num_groups = that call's result): per group the non-zero bins in ascending table-wide value id, as

@@ -63,6 +63,8 @@ PA_ACC_COUNT_U64, PA_ACC_SUM_I64, PA_ACC_SUM_F64, PA_ACC_MIN_I64, PA_ACC_MAX_I64
     PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64, PA_ACC_KEYBITS_U32, \
     PA_ACC_LANE_COUNT_U64 = range(13)
 PA_MAX_PERCENTILES = 64
+PA_TRIM_KEY_COLUMN, PA_TRIM_COUNT, PA_TRIM_AGG, PA_TRIM_AVG, PA_TRIM_RANGE = range(5)
+PA_MAX_TRIM_TERMS = 4
 ABI_VERSION = 5
 
 # every symbol declared in include/pinot_amd.h
@@ -81,7 +83,7 @@ EXPORTED = [
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
     "pa_query_partition_keys",
     "pa_query_accumulator_bytes", "pa_query_set_accumulator_buffer", "pa_query_num_sections", "pa_query_section",
-    "pa_query_fetch", "pa_query_fetch_histogram", "pa_query_percentiles", "pa_query_matched_docs", "pa_query_key_layout", "pa_query_limit_trimming",
+    "pa_query_fetch", "pa_query_fetch_trimmed", "pa_query_fetch_histogram", "pa_query_percentiles", "pa_query_matched_docs", "pa_query_key_layout", "pa_query_limit_trimming",
     "pa_query_num_groups_limit_reached", "pa_query_stats", "pa_query_leaf_bitmap_words", "pa_query_leaf_bitmaps",
     "pa_bitmap_counts_scratch_bytes", "pa_bitmap_counts", "pa_query_filter_counts",
     "pa_query_plan", "pa_query_column_staged", "pa_query_leap_leaf", "pa_query_leap_counts",
@@ -176,6 +178,15 @@ class ExprSpec(ctypes.Structure):
     ]
 
 
+class TrimSpec(ctypes.Structure):
+    _fields_ = [
+        ("num_terms", ctypes.c_int32),
+        ("kind", ctypes.c_int32 * PA_MAX_TRIM_TERMS), ("index", ctypes.c_int32 * PA_MAX_TRIM_TERMS),
+        ("index2", ctypes.c_int32 * PA_MAX_TRIM_TERMS), ("desc", ctypes.c_int32 * PA_MAX_TRIM_TERMS),
+        ("trim", ctypes.c_int64),
+    ]
+
+
 class LeafParams(ctypes.Structure):
     _fields_ = [
         ("lo", ctypes.c_int32), ("hi", ctypes.c_int32), ("negate", ctypes.c_int32), ("reserved", ctypes.c_int32),
@@ -238,6 +249,7 @@ def _declare(lib):
         "pa_query_num_sections": (i32, [vp]),
         "pa_query_section": (vp, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i64)]),
         "pa_query_fetch": (i64, [vp, vp, i64, vp, vp, vp]),
+        "pa_query_fetch_trimmed": (i64, [vp, vp, ctypes.POINTER(TrimSpec), i64, vp, vp, vp, ctypes.POINTER(i64)]),
         "pa_query_fetch_histogram": (i64, [vp, vp, i32, i64, i64, vp, vp, vp]),
         "pa_query_percentiles": (ctypes.c_int, [vp, vp, i32, i64, i32, vp, vp]),
         "pa_query_matched_docs": (i64, [vp]),

@@ -19,7 +19,7 @@ SOURCES = ["pa_scan_lane_lm.hip", "pa_scan_std.hip", "pa_scan_part_mv.hip", "pa_
            "pa_scan_select.hip", "pa_plan.hip",
            "pa_jit.hip", "pa_plan_kernels.hip", "pa_select.hip", "pa_distinct.hip", "pa_fetch.hip", "pa_capi.hip",
            "pa_compact.hip", "pa_segment.hip", "pa_hist.hip", "pa_prep.hip", "pa_launch_scan.hip", "pa_merge.hip",
-           "pa_pve.hip"]
+           "pa_pve.hip", "pa_trim.hip"]
 # every header under csrc/ (globbed, so a new one is covered without an edit here) and the public C-ABI header
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "pinot_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics", "-std=c++17",

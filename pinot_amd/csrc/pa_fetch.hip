@@ -1,5 +1,6 @@
-// Results: pa_query_fetch (compaction of the non-empty keys, one DMA per column) and the hashed key space's row
-// pack / merge for the cross-GPU exchange.
+// Results: pa_query_fetch (compaction of the non-empty keys, one DMA per column), pa_query_fetch_trimmed (the same for
+// the groups the server trim keeps, selected on the GPU: pa_trim.hip) and the hashed key space's row pack / merge for
+// the cross-GPU exchange.
 #include "pa_host.h"
 
 // A query whose tunings skip work in a kernel (pa_query_results_invalid) can be executed and timed, not read
@@ -290,6 +291,179 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
   }
   decode(rows, (const uint64_t*)hsec[0], [&](int sec) { return hsec[sec]; }, [&](int64_t r, int) { return hkeys[r]; },
          false, nullptr);
+  return m;
+}
+
+// Bytes of word `x < bound`'s digits that can differ between candidates (the passes above them are skipped)
+static int bytes_below(uint64_t bound) {
+  int b = 1;
+  while (b < 8 && (bound - 1) >> (8 * b)) ++b;
+  return b;
+}
+
+int64_t pa_query_fetch_trimmed(pa_query* q, void* stream, const pa_trim_spec* spec, int64_t capacity,
+                               int64_t* out_keys, int64_t* out_counts, void* const* out_aggs,
+                               int64_t* out_total_groups) {
+  if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
+  if (!spec) return fail(PA_EINVAL, "fetch trimmed: null spec");
+  if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "fetch trimmed: not a group-by query");
+  if (int rc = refuse_invalid(q)) return rc;
+  const pa_query_spec& s = q->spec;
+  if (q->hashed) return fail(PA_EUNSUPPORTED, "device group trim needs a direct key space");
+  if (q->is_filtered) return fail(PA_EUNSUPPORTED, "device group trim: the query has aggregation filters");
+  for (int a = 0; a < s.num_aggs; ++a)
+    if (s.aggs[a].type == PA_AGG_VALUE_HISTOGRAM)
+      return fail(PA_EUNSUPPORTED, "device group trim: the query has a VALUE_HISTOGRAM aggregation");
+  if (spec->num_terms < 0) return fail(PA_EINVAL, "fetch trimmed: negative term count");
+  if (spec->num_terms > PA_MAX_TRIM_TERMS) return fail(PA_EUNSUPPORTED, "device group trim: too many ORDER BY terms");
+  const int64_t K = q->num_keys;
+  TrimWordsDesc w;
+  std::memset(&w, 0, sizeof(w));
+  w.nterms = spec->num_terms;
+  w.ngb = s.num_group_by;
+  for (int j = 0; j < s.num_group_by; ++j) w.card[j] = s.group_by_cardinality[j];
+  auto agg_is = [&](int a, int type) { return a >= 0 && a < s.num_aggs && s.aggs[a].type == type; };
+  for (int e = 0; e < spec->num_terms; ++e) {
+    const int a = spec->index[e], b = spec->index2[e];
+    w.kind[e] = spec->kind[e];
+    w.a[e] = a;
+    w.b[e] = b;
+    w.desc[e] = spec->desc[e] ? 1 : 0;
+    switch (spec->kind[e]) {
+      case PA_TRIM_KEY_COLUMN: {
+        if (a < 0 || a >= s.num_group_by) return fail(PA_EINVAL, "fetch trimmed: bad group-by position");
+        int64_t st = 1;
+        for (int j = 0; j < a; ++j) st *= s.group_by_cardinality[j];
+        w.kstride[e] = st;
+        w.kcard[e] = s.group_by_cardinality[a];
+        break;
+      }
+      case PA_TRIM_COUNT: break;
+      case PA_TRIM_AGG:
+        if (a < 0 || a >= s.num_aggs) return fail(PA_EINVAL, "fetch trimmed: bad aggregation index");
+        if (!agg_is(a, PA_AGG_SUM) && !agg_is(a, PA_AGG_MIN) && !agg_is(a, PA_AGG_MAX))
+          return fail(PA_EUNSUPPORTED, "device group trim orders by SUM / MIN / MAX aggregations only");
+        break;
+      case PA_TRIM_AVG:
+        if (!agg_is(a, PA_AGG_SUM)) return fail(PA_EINVAL, "fetch trimmed: AVG needs a SUM aggregation");
+        break;
+      case PA_TRIM_RANGE:
+        if (!agg_is(a, PA_AGG_MAX) || !agg_is(b, PA_AGG_MIN))
+          return fail(PA_EINVAL, "fetch trimmed: RANGE needs a MAX and a MIN aggregation");
+        break;
+      default: return fail(PA_EINVAL, "fetch trimmed: unknown term kind");
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const bool grouped = s.num_group_by != 0;
+  const int all = grouped ? 0 : 1;
+  const unsigned long long* count = (const unsigned long long*)q->sections[0].ptr;
+
+  // candidates: how many non-empty groups there are (the fetch's own count + scan pass)
+  const int64_t nb = (K + 2047) / 2048;
+  if ((int64_t)q->fetch_blocks.n < (nb + 1) * 4) {
+    dev_free(q->fetch_blocks);
+    if (int rc = dev_alloc(q->fetch_blocks, (size_t)(nb + 1) * 4)) return rc;
+  }
+  uint32_t* blocks = (uint32_t*)q->fetch_blocks.p;
+  uint32_t total = 0;
+  uint64_t md[4] = {0, 0, 0, 0};
+  PA_HIP(launch_compact(count, K, all, blocks, 0, nullptr, 0, st));
+  PA_HIP(hipMemcpyAsync(&total, blocks + nb, 4, hipMemcpyDeviceToHost, st));
+  PA_HIP(hipMemcpyAsync(md, q->sections.back().ptr, 32, hipMemcpyDeviceToHost, st));
+  PA_HIP(hipStreamSynchronize(st));
+  const int64_t n = (int64_t)total;
+  if (out_total_groups) *out_total_groups = n;
+  const int64_t trim = std::max<int64_t>(spec->trim, 0);
+  if (n <= trim || !grouped) return pa_query_fetch(q, stream, capacity, out_keys, out_counts, out_aggs);
+  q->last_matched = (int64_t)md[0];
+  q->last_reached = (int64_t)md[2];
+  q->scanned_since_fetch = false;
+  if (md[1]) return fail(PA_EUNSUPPORTED, "group-key table overflow (more distinct groups than slots)");
+  if (md[3]) return fail(PA_EHIP, "internal: partitioned passes disagree on record counts");
+  const int64_t m = trim;
+  if (m == 0 || capacity < m) return m;
+
+  // the output columns of the kept groups, in pa_query_fetch's staging layout
+  FinalDesc f;
+  std::memset(&f, 0, sizeof(f));
+  f.nagg = s.num_aggs;
+  std::vector<size_t> off(s.num_aggs, 0);
+  size_t bytes = ((size_t)m * 16 + 255) & ~(size_t)255;  // keys | counts
+  for (int a = 0; a < s.num_aggs; ++a) {
+    const pa_agg_spec& A = s.aggs[a];
+    f.type[a] = A.type;
+    f.src[a] = q->hq.aggs[a].src;
+    f.sec[a] = q->agg_section[a] >= 0 ? q->sections[q->agg_section[a]].ptr : nullptr;
+    f.per[a] = A.type == PA_AGG_DISTINCTCOUNT ? presence_stride(A)
+               : (A.type == PA_AGG_DISTINCTCOUNTHLL ? (int64_t(1) << A.log2m) : 8);
+    off[a] = bytes;
+    bytes += ((size_t)m * (size_t)f.per[a] + 255) & ~(size_t)255;
+  }
+  if (q->fetch_stage.n < bytes) {
+    dev_free(q->fetch_stage);
+    if (int rc = dev_alloc(q->fetch_stage, bytes)) return rc;
+  }
+  char* ds = (char*)q->fetch_stage.p;
+  f.keys = (int64_t*)ds;
+  f.counts = (int64_t*)(ds + (size_t)m * 8);
+  for (int a = 0; a < s.num_aggs; ++a) f.out[a] = ds + off[a];
+
+  // scratch: candidate keys | order words | flags | kept candidates | control | histograms | states
+  const int nwords = spec->num_terms + 1;
+  const size_t col = ((size_t)n * 8 + 255) & ~(size_t)255;
+  const size_t ctl_bytes = (sizeof(TrimCtl) + 255) & ~(size_t)255;
+  const size_t hist_bytes = (size_t)kTrimMaxPasses * 256 * 4;
+  const size_t need = col * (size_t)(nwords + 3) + ctl_bytes + hist_bytes + (size_t)n;
+  if (q->trim_buf.n < need) {
+    dev_free(q->trim_buf);
+    if (int rc = dev_alloc(q->trim_buf, need)) return rc;
+  }
+  char* tb = (char*)q->trim_buf.p;
+  int64_t* cand = (int64_t*)tb;
+  w.words = (uint64_t*)(tb + col);
+  TrimPlan p;
+  std::memset(&p, 0, sizeof(p));
+  p.n = n;
+  p.words = w.words;
+  p.flag = (unsigned long long*)(tb + col * (size_t)(nwords + 1));
+  int64_t* sel = (int64_t*)(tb + col * (size_t)(nwords + 2));
+  p.ctl = (TrimCtl*)(tb + col * (size_t)(nwords + 3));
+  p.hist = (uint32_t*)((char*)p.ctl + ctl_bytes);
+  p.state = (uint8_t*)p.hist + hist_bytes;
+  // digit passes, most significant first: a key column's id and the tie word are below their cardinality / the key
+  // count, so their high bytes are the same in every candidate
+  for (int e = 0; e < nwords; ++e) {
+    int nbytes = 8;
+    if (e == spec->num_terms) nbytes = bytes_below((uint64_t)K);
+    else if (spec->kind[e] == PA_TRIM_KEY_COLUMN) nbytes = bytes_below((uint64_t)w.kcard[e]);
+    for (int b = nbytes - 1; b >= 0; --b) {
+      p.word[p.npass] = e;
+      p.shift[p.npass] = 8 * b;
+      ++p.npass;
+    }
+  }
+  CompactDesc d;
+  std::memset(&d, 0, sizeof(d));
+  d.keys = cand;
+  PA_HIP(launch_compact(count, K, all, blocks, n, &d, 1, st));
+  PA_HIP(launch_trim_words(count, &f, &w, cand, n, st));
+  PA_HIP(launch_trim_select(&p, m, st));
+  // the kept candidates in ascending order: the same count + scan + gather over the flags (n <= K: the block sums fit)
+  const int64_t nb2 = (n + 2047) / 2048;
+  d.keys = sel;
+  PA_HIP(launch_compact(p.flag, n, 0, blocks, 0, nullptr, 0, st));
+  PA_HIP(launch_compact(p.flag, n, 0, blocks, m, &d, 1, st));
+  PA_HIP(launch_trim_rows(count, cand, sel, n, m, &f, st));
+  uint32_t kept = 0;
+  PA_HIP(hipMemcpyAsync(&kept, blocks + nb2, 4, hipMemcpyDeviceToHost, st));
+  if (out_keys) PA_HIP(hipMemcpyAsync(out_keys, f.keys, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  if (out_counts) PA_HIP(hipMemcpyAsync(out_counts, f.counts, (size_t)m * 8, hipMemcpyDeviceToHost, st));
+  for (int a = 0; a < s.num_aggs; ++a)
+    if (out_aggs && out_aggs[a])
+      PA_HIP(hipMemcpyAsync(out_aggs[a], f.out[a], (size_t)m * (size_t)f.per[a], hipMemcpyDeviceToHost, st));
+  PA_HIP(hipStreamSynchronize(st));
+  if ((int64_t)kept != m) return fail(PA_EHIP, "internal: the group trim kept a wrong number of groups");
   return m;
 }
 

@@ -241,6 +241,7 @@ struct pa_query {
   void* host_acc = nullptr;  // pinned copy of the accumulator block (small-block fetch path)
   DevBuf fetch_blocks, fetch_stage;  // large-key fetch: per-block counts / compacted rows
   void* fetch_host = nullptr;        // pinned copy of the compacted rows
+  DevBuf trim_buf;  // pa_query_fetch_trimmed: candidate keys, order words, states, histograms (grown on demand)
   int lane_major = 0;
   int eq_prefilter = 0;  // some segment's plan takes the equality prefilter (LmSegPlan::flags)
   int stream_nt = 0;     // the hoisted loops' column DMAs carry the nt policy
@@ -396,6 +397,7 @@ struct pa_query {
     if (host_acc) (void)hipHostFree(host_acc);
     dev_free(fetch_blocks);
     dev_free(fetch_stage);
+    dev_free(trim_buf);
     if (fetch_host) (void)hipHostFree(fetch_host);
     dev_free(acc);
     for (auto& b : owned) dev_free(b);

@@ -1,5 +1,5 @@
 // Host-callable launchers of the kernel units (pa_kernels.hip, pa_prep.hip, pa_compact.hip, pa_launch_scan.hip,
-// pa_merge.hip, pa_stats.hip, pa_pve.hip) with their descriptors, and the kernel-pointer getters of the scan units.
+// pa_merge.hip, pa_stats.hip, pa_pve.hip, pa_trim.hip) with their descriptors, and the kernel-pointer getters of the scan units.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "pa_device.h"
@@ -31,6 +31,47 @@ struct FinalDesc {
 };
 hipError_t launch_compact_final(const unsigned long long* count, int64_t K, int all, const uint32_t* block_off,
                                 int64_t cap, const FinalDesc* d, hipStream_t s);
+// Group trim on the GPU (pa_trim.hip, pa_query_fetch_trimmed): per candidate group (a non-empty key, ascending) a string
+// of 64-bit order words, most significant first — one per ORDER BY term, then the tie word — and an MSB radix select of
+// the `trim` smallest strings, 8 bits per pass. NaN term values are out of scope (the host comparator is no total order
+// over them).
+constexpr int kTrimMaxWords = PA_MAX_TRIM_TERMS + 1;
+constexpr int kTrimMaxPasses = kTrimMaxWords * 8;
+struct TrimWordsDesc {
+  int32_t nterms, ngb;
+  int32_t kind[PA_MAX_TRIM_TERMS];   // PA_TRIM_*
+  int32_t a[PA_MAX_TRIM_TERMS];      // group-by position, or aggregation (RANGE: its MAX)
+  int32_t b[PA_MAX_TRIM_TERMS];      // RANGE: its MIN
+  int32_t desc[PA_MAX_TRIM_TERMS];   // the word is complemented
+  int64_t kstride[PA_MAX_TRIM_TERMS], kcard[PA_MAX_TRIM_TERMS];  // KEY_COLUMN: id = key / kstride % kcard
+  int64_t card[PA_MAX_GROUP_BY];     // table-wide cardinality per group-by position (key digit j has weight prod card_k, k < j)
+  uint64_t* words;                   // [nterms + 1][n]
+};
+struct TrimCtl {                     // one per select, in device memory
+  unsigned long long k;              // candidates still to take from the undecided class
+  const uint64_t* pend_words;        // the last pick, not yet applied to the states: digit (word >> pend_shift) & 255
+  int32_t pend_shift, pend_bin;      //   below pend_bin = IN, above = OUT, equal = still undecided
+  int32_t pending, done, rest_in;    // done: the undecided class is taken whole (rest_in) or not at all
+  int32_t pad;
+  uint32_t ticket[kTrimMaxPasses];   // workgroups that flushed their histogram, per pass
+};
+struct TrimPlan {
+  int64_t n;                         // candidates
+  const uint64_t* words;             // [nwords][n]
+  uint8_t* state;                    // [n]: 0 undecided, 1 IN, 2 OUT
+  uint32_t* hist;                    // [npass][256]
+  TrimCtl* ctl;
+  unsigned long long* flag;          // [n] out: 1 = kept
+  int32_t npass;
+  int32_t word[kTrimMaxPasses], shift[kTrimMaxPasses];  // the digit of every pass, most significant first
+};
+hipError_t launch_trim_words(const unsigned long long* count, const FinalDesc* f, const TrimWordsDesc* w,
+                             const int64_t* keys, int64_t n, hipStream_t s);
+// state, histograms and control block to zero, k = trim; the passes; then flag[i] = candidate i is kept
+hipError_t launch_trim_select(const TrimPlan* p, int64_t trim, hipStream_t s);
+// rows r < m of the fetch staging layout (FinalDesc) from candidates sel[r] < n (ascending): key keys[sel[r]]
+hipError_t launch_trim_rows(const unsigned long long* count, const int64_t* keys, const int64_t* sel, int64_t n,
+                            int64_t m, const FinalDesc* d, hipStream_t s);
 // one filter literal of one segment -> doc bitmap (execution statistics)
 hipError_t launch_leaf_bitmap(const DevSeg* seg, int li, int flip, int64_t num_docs, uint32_t* out, hipStream_t s);
 // Execution-statistics counts over leaf bitmaps (pa_bitmap_counts, pa_query_filter_counts): per job, postfix

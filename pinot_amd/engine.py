@@ -710,15 +710,20 @@ class GpuQueryExecutor:
         out["plan"]["results_invalid"] = int(L.lib().pa_query_results_invalid(self.handle))
         return out
 
-    def fetch_arrays(self, stream=None, pooled=False):
+    def fetch_arrays(self, stream=None, pooled=False, trim_spec=None):
         """Non-empty groups in ascending table-wide key order as arrays: (keys int64[n], counts int64[n],
         [one array per GPU accumulator: float64[n], or uint8[n << log2m] HLL registers]). Synchronises `stream`.
         pooled=True: the arrays are views of the process's page-locked output pool (OUTPUT_POOL: each column arrives by
-        one DMA; valid until the next pooled fetch of any executor) instead of fresh arrays."""
+        one DMA; valid until the next pooled fetch of any executor) instead of fresh arrays.
+        trim_spec (a _lib.TrimSpec, trim.build_spec): only the groups the server trim keeps, chosen on the GPU
+        (pa_query_fetch_trimmed); self.trim_total_groups is then the number of non-empty groups."""
         lib = L.lib()
         alloc = (lambda slot, n, dt: OUTPUT_POOL.array(slot, n, dt)) if pooled else (lambda slot, n, dt: np.empty(n, dt))
         cap = 1 if not self.query.group_by else min(self.num_keys, 1 << 16)
-        if self.query.group_by and self.num_keys > 1 << 16:
+        if trim_spec is not None:
+            cap = max(1, min(self.num_keys, int(trim_spec.trim)))
+            total = ctypes.c_int64(0)
+        elif self.query.group_by and self.num_keys > 1 << 16:
             # large key space: a capacity-0 call runs only the GPU count pass and returns the number of non-empty
             # groups, so the gather + copy run once, at the exact size
             cap = max(1, L.check(lib.pa_query_fetch(self.handle, stream, 0, None, None, None), "pa_query_fetch"))
@@ -739,8 +744,14 @@ class GpuQueryExecutor:
                     o = alloc(i, cap, np.float64)
                 outs.append(o)
                 ptrs[i] = o.ctypes.data
-            n = L.check(lib.pa_query_fetch(self.handle, stream, cap, keys.ctypes.data, counts.ctypes.data, ptrs),
-                        "pa_query_fetch")
+            if trim_spec is not None:
+                n = L.check(lib.pa_query_fetch_trimmed(self.handle, stream, ctypes.byref(trim_spec), cap,
+                                                       keys.ctypes.data, counts.ctypes.data, ptrs, ctypes.byref(total)),
+                            "pa_query_fetch_trimmed")
+                self.trim_total_groups = int(total.value)
+            else:
+                n = L.check(lib.pa_query_fetch(self.handle, stream, cap, keys.ctypes.data, counts.ctypes.data, ptrs),
+                            "pa_query_fetch")
             if n <= cap:
                 break
             cap = n
@@ -961,15 +972,49 @@ class GpuQueryExecutor:
             in_filter += hi
         return in_filter, post
 
-    def fetch(self, stream=None, execution_stats=True) -> IntermediateResult:
+    def fetch(self, stream=None, execution_stats=True, server_trim=False) -> IntermediateResult:
         """The results block of the last scan. Like the reference's results blocks (BaseResultsBlock.java:194) it carries
         the execution statistics — numEntriesScannedInFilter / PostFilter from pa_query_execution_stats, after the groups
-        (execution_stats): execution_stats=False leaves them 0."""
-        lib = L.lib()
+        (execution_stats): execution_stats=False leaves them 0.
+        server_trim=True: the block after the server's group trim, reduce.server_trim(self.fetch(...), query), with the
+        kept groups chosen on the GPU and only their rows copied (pa_query_fetch_trimmed; trim.py). Shapes the device
+        refuses take the full fetch and the host trim, so the answer is the same either way; self.last_trim =
+        {"device": the GPU trimmed, "groups": non-empty groups, "kept": groups in the block}."""
         q = self.query
         if self.handle is None:
+            self.last_trim = {"device": False, "groups": 0, "kept": 0}
             return self._empty_result()
-        keys, counts, outs = self.fetch_arrays(stream, pooled=True)  # (converted to Python objects below)
+        if server_trim:
+            from . import reduce as R
+            from . import trim as TR
+            spec = None
+            if q.group_by:
+                try:
+                    spec = TR.build_spec(TR.lower_order_by(q, self.agg_map, self.hashed), TR.trim_size(q))
+                except TR.HostTrim:
+                    pass
+            arrays = None
+            if spec is not None:
+                try:
+                    arrays = self.fetch_arrays(stream, pooled=True, trim_spec=spec)
+                except L.PinotAmdError as e:
+                    if getattr(e, "code", None) != L.PA_EUNSUPPORTED:
+                        raise
+            if arrays is None:
+                full = self.fetch(stream, execution_stats)
+                res = R.server_trim(full, q)
+                self.last_trim = {"device": False, "groups": len(full.groups) if q.group_by else 1,
+                                  "kept": len(res.groups) if q.group_by else 1}
+                return res
+            self.last_trim = {"device": True, "groups": self.trim_total_groups, "kept": len(arrays[0])}
+            return self._result_from_arrays(arrays, stream, execution_stats)
+        return self._result_from_arrays(self.fetch_arrays(stream, pooled=True), stream, execution_stats)
+
+    def _result_from_arrays(self, arrays, stream, execution_stats):
+        """fetch_arrays' columns (of every non-empty group, or of the trimmed ones) as the IntermediateResult."""
+        lib = L.lib()
+        q = self.query
+        keys, counts, outs = arrays  # (converted to Python objects below)
         n = len(keys)
         res = IntermediateResult(list(q.aggregations), list(q.group_by))
         res.num_total_docs = sum(s.num_docs for s in self.all_segs)

@@ -12,7 +12,10 @@
              (a) configs[1]'s table, DISTINCT daysSinceEpoch under the 10 % filter (LDS bitmap); (b) configs[2]'s table,
              DISTINCT d1, d2 over every doc (1024 x 1024 keys), as the planner runs it and with distinct_lds = 0
 
-python tools/bench_configs.py [--workload highcard|star|selection|distinct|all] [--segments S] [--docs D] [--reps R]
+  trim     : configs[2]'s table and GROUP BY with ORDER BY SUM(m) DESC LIMIT 10: (a) the full fetch plus
+             reduce.server_trim on the host against (b) the trimmed fetch (pa_query_fetch_trimmed) on the same executor
+
+python tools/bench_configs.py [--workload highcard|star|selection|distinct|trim|all] [--segments S] [--docs D] [--reps R]
 Prints one JSON line per (workload, plan): scan-kernel ms per launch (HIP events around back-to-back launches on
 the launch stream), rows/s, forward-index bytes staged per launch and GB/s, fetch ms, groups.
 """
@@ -475,6 +478,67 @@ def run_distinct(nseg, docs, reps, warm=0, tuning=None):
             g.close()
 
 
+TRIM_SQL = ("SELECT d1, d2, SUM(m), MIN(m), MAX(m) FROM t GROUP BY d1, d2 ORDER BY SUM(m) DESC LIMIT 10 "
+            "OPTION(numGroupsLimit=2000000)")
+
+
+def run_trim(nseg, docs, reps, tuning=None):
+    """The group trim line: configs[2] with ORDER BY SUM(m) DESC LIMIT 10 on one executor. (a) host_trim: the full fetch
+    (every non-empty group to the host and into Python objects) plus reduce.server_trim — what a server did before the
+    device trim, the yardstick; (b) device_trim: fetch(server_trim=True). Per side the device part (HIP events around
+    the fetch_arrays call on the launch stream: kernels and copies) and the wall time of the whole call, medians of
+    `reps`; the two blocks are compared."""
+    import torch
+    from pinot_amd import parse_sql
+    from pinot_amd import trim as TR
+    from pinot_amd.engine import GpuQueryExecutor, GpuSegment
+    from pinot_amd.reduce import server_trim
+    gsegs = [GpuSegment(highcard_segment(100 + i, docs), device=0) for i in range(nseg)]
+    q = parse_sql(TRIM_SQL)
+    ex = GpuQueryExecutor(q, gsegs, tuning=tuning)
+    stream = torch.cuda.current_stream()
+    sp = stream.cuda_stream
+    ex.execute(sp)
+    torch.cuda.synchronize()
+    spec = TR.build_spec(TR.lower_order_by(q, ex.agg_map, ex.hashed), TR.trim_size(q))
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def device_ms(trim_spec):
+        ex.fetch_arrays(sp, pooled=True, trim_spec=trim_spec)  # (warms the allocations)
+        out = []
+        for _ in range(reps):
+            a.record(stream)
+            ex.fetch_arrays(sp, pooled=True, trim_spec=trim_spec)
+            b.record(stream)
+            torch.cuda.synchronize()
+            out.append(a.elapsed_time(b))
+        return float(np.median(out))
+
+    def wall_ms(fn):
+        out, res = [], None
+        for _ in range(reps):
+            t = time.perf_counter()
+            res = fn()
+            out.append((time.perf_counter() - t) * 1e3)
+        return float(np.median(out)), res
+
+    host_dev = device_ms(None)
+    dev_dev = device_ms(spec)
+    host_wall, want = wall_ms(lambda: server_trim(ex.fetch(sp, execution_stats=False), q))
+    dev_wall, got = wall_ms(lambda: ex.fetch(sp, execution_stats=False, server_trim=True))
+    lt = dict(ex.last_trim)
+    assert lt["device"] and got.groups == want.groups, lt
+    print(json.dumps({"workload": "trim", "plan_name": "order_by_sum_desc_limit10", "sql": TRIM_SQL,
+                      "groups": lt["groups"], "kept": lt["kept"],
+                      "host_trim": {"device_ms": round(host_dev, 3), "wall_ms": round(host_wall, 2)},
+                      "device_trim": {"device_ms": round(dev_dev, 3), "wall_ms": round(dev_wall, 2)},
+                      "wall_speedup": round(host_wall / dev_wall, 2), "plan": ex.stats()["plan"],
+                      "segments": nseg, "docs_per_segment": docs, "reps": reps}), flush=True)
+    ex.close()
+    for g in gsegs:
+        g.close()
+
+
 def run(workload, nseg, docs, reps, only=None, no_stepmajor=False, variants=None, cpu_sample=0, exec_stats=False,
         warm=0, check=False, tuning=None):
     import torch
@@ -634,6 +698,9 @@ def main():
     torch.cuda.set_device(0)
     if args.workload == "distinct":
         run_distinct(args.segments, args.docs, args.reps, args.warm, tuning)
+        return
+    if args.workload == "trim":
+        run_trim(args.segments, args.docs, args.reps, tuning)
         return
     if args.workload == "selection":
         run_selection(args.segments, args.docs, args.reps, args.warm, args.check, tuning, args.cpu_sample)
