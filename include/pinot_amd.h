@@ -45,6 +45,13 @@
  *      data/table/TableResizer.java:187-238 (resizeRecordsMap: the top `trim` records under the ORDER BY comparator) at
  *      the capacity of GroupByUtils.getTableCapacity / operator/combine/GroupByCombineOperator.java:63-73 — an MSB
  *      radix select over order words in HBM, then a gather of the kept groups' rows only.
+ *  pa_query_fetch_time_rows / pa_query_time_row_form (PA_AGG_LAST_ROW_BY_TIME / PA_AGG_FIRST_ROW_BY_TIME)
+ *      replace aggregation/function/LastWithTimeAggregationFunction.java and FirstWithTimeAggregationFunction.java with
+ *      their per-type subclasses ({First,Last}{Int,Long,Float,Double,String}ValueWithTimeAggregationFunction.java;
+ *      factory cases AggregationFunctionFactory.java:224-252 and :324-350): aggregate / aggregateGroupBySV (the doc with
+ *      time >= / <= the best so far takes over, :112,147,196 / :111,147,200) and the in-server merge (:223 / :227) become
+ *      one 64-bit max per group inside the scan; extractAggregationResult / extractGroupByResult (the ValueTimePair)
+ *      the winning (segment, doc) and the cells a finish kernel reads there.
  *  pa_query_set_selection / pa_query_bind_order_remap / pa_query_fetch_selection
  *      replace, for one segment set on one GPU, operator/query/SelectionOnlyOperator.java,
  *      operator/query/SelectionOrderByOperator.java:108-112 (the comparator), :139-188 (every ordered expression
@@ -141,6 +148,32 @@ extern "C" {
                                     PA_EUNSUPPORTED over a hashed key space, and for a raw or STRING / BYTES column. Read
                                     with pa_query_fetch_histogram / pa_query_percentiles; pa_query_fetch writes nothing
                                     for it */
+#define PA_AGG_LAST_ROW_BY_TIME 8  /* LASTWITHTIME: per group the doc with the greatest value of the time column
+                                      `column_id` (an SV INT / LONG column, raw or dictionary-encoded in every bound
+                                      segment). Within a segment docs are offered in docId order and a doc with time >=
+                                      the best takes over (LastWithTimeAggregationFunction.java:112,147,196), so among
+                                      docs of equal winning time the greatest docId wins. The reference merges segments in
+                                      a thread-dependent order (:223), so its ties across segments are unspecified; here:
+                                      among equal winning times the greatest (segment bind index, docId) wins. The
+                                      accumulator knows nothing of a value column: any column is read at the winning row
+                                      by pa_query_fetch_time_rows, so LASTWITHTIME(a, ts, ..) and LASTWITHTIME(b, ts, ..)
+                                      share one aggregation. A dictionary time column: num_values = size of its table-wide
+                                      dictionary, ids in value order, segment dictIds mapped by pa_query_bind_value_remap.
+                                      The scan keeps per group the maximum of one 64-bit word, time key << row bits |
+                                      (segment << doc bits | doc) + 1 (0 = no row; "packed", one launch), or — a raw time
+                                      column whose range does not fit beside the row — the maximum time in one launch and
+                                      the maximum row among the docs holding it in a second ("wide"):
+                                      pa_query_time_row_form. pa_query_prepare fails with PA_EUNSUPPORTED over a hashed
+                                      key space (so over raw group-by columns and expression keys), for a multi-value
+                                      group-by or aggregation column in the query, for a time column that is multi-value,
+                                      not INT / LONG, or dictionary-encoded in some bound segments only, next to
+                                      aggregation filters or expressions, and where numGroupsLimit trimming would run in
+                                      its first-position + sort form (the prefix walk admits these updates like any
+                                      other). pa_query_fetch writes nothing for it */
+#define PA_AGG_FIRST_ROW_BY_TIME 9 /* FIRSTWITHTIME: the same with the smallest time (a doc with time <= the best takes
+                                      over, FirstWithTimeAggregationFunction.java:111,147,200: among equal winning times
+                                      again the greatest (segment bind index, docId) wins); the time key is complemented
+                                      inside its width */
 /* SUM / MIN / MAX / DISTINCTCOUNTHLL over a multi-value column aggregate every value of the doc (SUMMV, MINMV, MAXMV,
  * DISTINCTCOUNTHLLMV); a multi-value group-by column expands a doc into one key per value (cartesian product over
  * several MV columns), as DictionaryBasedGroupKeyGenerator.getIntRawKeys does. */
@@ -195,8 +228,8 @@ typedef struct {
   int32_t column_id; /* ignored for COUNT */
   int32_t log2m;     /* DISTINCTCOUNTHLL only (CommonConstants.Helix.DEFAULT_HYPERLOGLOG_LOG2M = 8) */
   int32_t flags;     /* PA_AGGF_* */
-  int64_t num_values; /* DISTINCTCOUNT / VALUE_HISTOGRAM: size of the column's table-wide value dictionary (ignored
-                         otherwise) */
+  int64_t num_values; /* DISTINCTCOUNT / VALUE_HISTOGRAM, and LAST / FIRST_ROW_BY_TIME over a dictionary time column: size
+                         of the column's table-wide value dictionary (ignored otherwise) */
 } pa_agg_spec;
 
 /* SUM over an INT/LONG column: keep the exact 96-bit (low 32 unsigned, high 32 signed) pair accumulator
@@ -296,7 +329,9 @@ int pa_query_bind_segment(pa_query* q, int32_t index, const pa_segment* seg,
 
 /* DISTINCTCOUNT or VALUE_HISTOGRAM aggregation `agg` on the segment bound at `index`: remap[d] = the table-wide value id of the segment's
  * dictId d (int32[segment cardinality]; NULL = identity, the segment's dictionary IS the table-wide one). Call after
- * pa_query_bind_segment, before pa_query_prepare. */
+ * pa_query_bind_segment, before pa_query_prepare. Also a LAST / FIRST_ROW_BY_TIME aggregation whose time column is
+ * dictionary-encoded in that segment: the table-wide ids must follow the order of the values (PA_EINVAL for a raw time
+ * column, whose values the scan reads directly). */
 int pa_query_bind_value_remap(pa_query* q, int32_t index, int32_t agg, const int32_t* remap);
 
 /* ---------------------------------------------------------------- selection queries
@@ -568,6 +603,12 @@ int pa_query_scan(pa_query* q, void* stream);
                                  present; the only per-key section of such a query (reset identity 0) */
 #define PA_ACC_LANE_COUNT_U64 12 /* reduce SUM; filtered aggregations: [lane * num_keys + key] = docs of that lane (W AND
                                     F_lane) in that group (reset identity 0) */
+#define PA_ACC_TIME_ROW_U64 13 /* LAST / FIRST_ROW_BY_TIME: [key] = the group's winning word (packed form: time key <<
+                                  row bits | row + 1; wide form: row + 1), reset identity 0 = no row. Not element-wise
+                                  reducible across GPUs: the segment index in the row is rank-local, and the row's values
+                                  live on the rank that holds it */
+#define PA_ACC_TIME_MAX_I64 14 /* the wide form's first word: [key] = the greatest time of the group's docs (FIRST: of
+                                  the complemented times), reset identity INT64_MIN; read by the second scan launch */
 /* All sections live in one device block of pa_query_accumulator_bytes() bytes (256-byte aligned sections).
  * pa_query_set_accumulator_buffer lets the caller own that block (e.g. memory its collective library
  * registered) instead of the library: call after pa_query_prepare; `bytes` must be >= the size. */
@@ -581,7 +622,8 @@ void* pa_query_section(const pa_query* q, int32_t section, int32_t* kind, int64_
  * out_keys: int64[capacity]; out_counts: int64[capacity]; out_aggs[i]: double[capacity] for
  * COUNT/SUM/MIN/MAX (the reference's intermediate type), uint8[capacity << log2m] for HLL registers. Nothing is
  * written for a VALUE_HISTOGRAM aggregation (0 bytes per group: its out_aggs[i] may be NULL); its bins are read with
- * pa_query_fetch_histogram / pa_query_percentiles.
+ * pa_query_fetch_histogram / pa_query_percentiles. Nor for a LAST / FIRST_ROW_BY_TIME aggregation (0 bytes per group):
+ * pa_query_fetch_time_rows reads its rows.
  * For aggregation-only queries key 0 is always returned (count may be 0).
  * Returns the number of groups (may exceed capacity: then only `capacity` were written), <0 on error.
  * capacity = 0 (output pointers may be NULL) only counts the groups — for large key spaces just the GPU count pass —
@@ -602,8 +644,8 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
  * key ids, group-by column 0 most significant, ascending. num_terms = 0 keeps the `trim` smallest key tuples. NaN term
  * values are out of scope: the comparator of the reference is no total order over them.
  * PA_EUNSUPPORTED (the caller trims the full fetch on the host instead): a hashed key space (so any expression key), a
- * query with a VALUE_HISTOGRAM aggregation or aggregation filters (their fetch calls follow the full fetch's group
- * order), more than PA_MAX_TRIM_TERMS terms, a term over any other aggregation type (HLL, DISTINCTCOUNT, COUNT_MV).
+ * query with a VALUE_HISTOGRAM or LAST / FIRST_ROW_BY_TIME aggregation or aggregation filters (their fetch calls follow
+ * the full fetch's group order), more than PA_MAX_TRIM_TERMS terms, a term over any other aggregation type (HLL, DISTINCTCOUNT, COUNT_MV).
  * HLL / DISTINCTCOUNT aggregations that are only read are gathered for the kept groups.
  * Returns min(n, trim) (may exceed capacity: then nothing was written; call again with that capacity), <0 on error;
  * *out_total_groups = n. With n <= trim the call is pa_query_fetch. Fills pa_query_matched_docs and
@@ -645,6 +687,26 @@ int64_t pa_query_fetch_histogram(pa_query* q, void* stream, int32_t agg, int64_t
 #define PA_MAX_PERCENTILES 64
 int pa_query_percentiles(pa_query* q, void* stream, int32_t agg, int64_t num_groups, int32_t num_percentiles,
                          const double* percentiles, int32_t* out_value_ids);
+
+/* The winning rows of LAST / FIRST_ROW_BY_TIME aggregation `agg` for the groups pa_query_fetch returns for the current
+ * accumulators, in the same order (num_groups = that call's result): group g's row is doc out_docs[g] of the segment
+ * bound at out_segments[g] (int32[num_groups] each, may be NULL); both are -1 for a group with no row (the
+ * aggregation-only key 0 when no doc matched). out_cells[c] (int64[num_groups], c < num_columns <=
+ * PA_MAX_SELECT_COLUMNS) takes column columns[c] at that row in pa_query_fetch_selection's cell convention: the
+ * segment's dictId for a dictionary column, the value of a raw INT / LONG column, the bits of the value as a double for a
+ * raw FLOAT / DOUBLE column (0 for a group with no row). The time itself is fetched by listing the time column. Columns
+ * must be single-value and not BYTES in every bound segment (PA_EUNSUPPORTED). Replaces
+ * {Last,First}WithTimeAggregationFunction.extractAggregationResult / extractGroupByResult (the ValueTimePair the scan's
+ * setValueTimePair calls kept): the word decodes to (segment, doc), and one thread per (group, column) reads the cell
+ * there (pa_select.hip). Synchronises `stream`. */
+int pa_query_fetch_time_rows(pa_query* q, void* stream, int32_t agg, int64_t num_groups, int32_t num_columns,
+                             const int32_t* columns, int32_t* out_segments, int32_t* out_docs, int64_t* const* out_cells);
+
+/* How the scan keeps LAST / FIRST_ROW_BY_TIME aggregation `agg`: 1 = packed (one word per group, one scan launch: time
+ * bits + row bits <= 63), 2 = wide (a raw time column whose range does not fit: two words and two launches of the scan;
+ * everything else the query computes accumulates in the first only), 0 = not such an aggregation, <0 = not prepared or
+ * no such aggregation index. Tuning time_rows_wide forces the wide form for raw time columns (pa_tuning.h). */
+int32_t pa_query_time_row_form(const pa_query* q, int32_t agg);
 
 /* numDocsScanned captured by the last pa_query_fetch (docs that passed the filter; with a multi-value group-by this
  * differs from the sum of the group counts), <0 on error. */

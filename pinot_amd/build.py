@@ -15,7 +15,7 @@ LIB = os.path.join(HERE, "libpinot_amd.so")
 # slowest first: with fewer cores than units, the long compiles start at once and the short ones fill in behind them
 SOURCES = ["pa_scan_lane_lm.hip", "pa_scan_std.hip", "pa_scan_part_mv.hip", "pa_scan_part_b.hip", "pa_scan_lane_raw.hip",
            "pa_scan_gdense.hip", "pa_scan_global.hip", "pa_scan_lane_dict.hip", "pa_kernels.hip", "pa_scan_part_a.hip",
-           "pa_scan_filtered.hip", "pa_scan_expr.hip", "pa_stats.hip", "pa_stats_host.hip", "pa_scan_lane_sm.hip", "pa_scan_distinct.hip",
+           "pa_scan_filtered.hip", "pa_scan_expr.hip", "pa_scan_trow.hip", "pa_stats.hip", "pa_stats_host.hip", "pa_scan_lane_sm.hip", "pa_scan_distinct.hip",
            "pa_scan_select.hip", "pa_plan.hip",
            "pa_jit.hip", "pa_plan_kernels.hip", "pa_select.hip", "pa_distinct.hip", "pa_fetch.hip", "pa_capi.hip",
            "pa_compact.hip", "pa_segment.hip", "pa_hist.hip", "pa_prep.hip", "pa_launch_scan.hip", "pa_merge.hip",

@@ -178,10 +178,12 @@ int pa_query_bind_value_remap(pa_query* q, int32_t index, int32_t agg, const int
   if (q->prepared) return fail(PA_EINVAL, "query already prepared");
   if (!q->segs[index]) return fail(PA_EINVAL, "bind the segment before its value remaps");
   const pa_agg_spec& A = q->spec.aggs[agg];
-  if (!value_id_agg(A.type))
-    return fail(PA_EINVAL, "value remaps belong to DISTINCTCOUNT and VALUE_HISTOGRAM aggregations");
+  if (!value_id_agg(A.type) && !time_row_agg(A.type))
+    return fail(PA_EINVAL, "value remaps belong to DISTINCTCOUNT, VALUE_HISTOGRAM and LAST / FIRST_ROW_BY_TIME aggregations");
   auto it = q->segs[index]->cols.find(A.column_id);
   if (it == q->segs[index]->cols.end()) return fail(PA_EINVAL, "aggregation column missing in segment");
+  if (time_row_agg(A.type) && it->second->kind != COL_SV_DICT)
+    return fail(PA_EINVAL, "a value remap for a time column that is not dictionary-encoded in this segment");
   q->vremaps[index][agg].clear();
   if (!remap) return PA_OK;
   const int32_t card = it->second->cardinality;
@@ -204,10 +206,11 @@ int pa_query_prepare(pa_query* q) {
   if (!rc) rc = plan_key_space(q, P);
   if (!rc) rc = plan_limit(q, P);
   // (a distinct query and a query with aggregation filters have their own two strategies each)
-  if (!rc && !q->is_distinct && !q->is_filtered && !q->is_expr) rc = plan_gdense(q, P);
+  if (!rc && !q->is_distinct && !q->is_filtered && !q->is_expr && !q->is_trow) rc = plan_gdense(q, P);
   if (!rc) rc = build_segments(q, P);
   if (!rc && q->is_filtered) rc = filtered_validate(q, P);
   if (!rc && q->is_expr) rc = expr_validate(q, P);
+  if (!rc) rc = trow_validate(q, P);
   if (!rc) rc = plan_walk(q, P);
   if (!rc) rc = plan_accumulators(q, P);
   TilePlan plan, count_plan;
@@ -236,6 +239,10 @@ int pa_query_prepare(pa_query* q) {
   }
   if (q->is_expr) {
     rc = expr_plan(q, P);
+    if (rc) return rc;
+  }
+  if (q->is_trow) {
+    rc = trow_plan(q);
     if (rc) return rc;
   }
   rc = plan_leaps(q, P);
@@ -306,6 +313,13 @@ int pa_query_prepare(pa_query* q) {
   if (rc) return rc;
   rc = upload_descriptors(q);
   if (rc) return rc;
+  if (q->trow_wide) {  // the second launch's descriptor: the same query, trow_pass = 2
+    rc = dev_alloc(q->dq_pass2, sizeof(DevQuery));
+    if (rc) return rc;
+    DevQuery h2 = q->hq;
+    h2.trow_pass = 2;
+    PA_HIP(hipMemcpy(q->dq_pass2.p, &h2, sizeof(DevQuery), hipMemcpyHostToDevice));
+  }
   if (!q->is_distinct) rc = jit_plan(q, P, cus);
   if (rc) return rc;
   if (q->is_distinct) {
@@ -333,7 +347,7 @@ int pa_query_reset(pa_query* q, void* stream) {
   // ones keep the memsets, whose rate matters there and whose extra launches no longer do.
   auto identity = [](const Section& sc, int64_t& v) {
     if (sc.kind == PA_ACC_MIN_I64 || sc.kind == PA_ACC_KEYS_I64) v = INT64_MAX;
-    else if (sc.kind == PA_ACC_MAX_I64) v = INT64_MIN;
+    else if (sc.kind == PA_ACC_MAX_I64 || sc.kind == PA_ACC_TIME_MAX_I64) v = INT64_MIN;
     else return false;
     return true;
   };
@@ -368,7 +382,8 @@ int pa_query_reset(pa_query* q, void* stream) {
   if (q->hq.leap_mode) PA_HIP(hipMemsetAsync(q->leap_buf.p, 0, leap_header_bytes(q), st));
   for (const Section& sc : q->sections) {
     if (sc.kind == PA_ACC_MIN_I64 || sc.kind == PA_ACC_KEYS_I64) PA_HIP(launch_fill_i64((int64_t*)sc.ptr, sc.n, INT64_MAX, st));
-    else if (sc.kind == PA_ACC_MAX_I64) PA_HIP(launch_fill_i64((int64_t*)sc.ptr, sc.n, INT64_MIN, st));
+    else if (sc.kind == PA_ACC_MAX_I64 || sc.kind == PA_ACC_TIME_MAX_I64)
+      PA_HIP(launch_fill_i64((int64_t*)sc.ptr, sc.n, INT64_MIN, st));
   }
   return PA_OK;
 }
@@ -465,6 +480,11 @@ int pa_query_scan(pa_query* q, void* stream) {
   PartScratch none{};
   PA_HIP(launch_scan(q->strategy, q->steps, q->lane_major, q->grid, q->lds_bytes, (const DevQuery*)q->dq.p,
                      (const DevSeg*)q->dsegs.p, (const LmSegPlan*)q->dplans.p, none, st));
+  // row by time, wide form: the same scan again (stream order: the first launch's time words are final), in which only
+  // the docs holding their key's winning time accumulate, and only into the row words
+  if (q->trow_wide)
+    PA_HIP(launch_scan(q->strategy, q->steps, q->lane_major, q->grid, q->lds_bytes, (const DevQuery*)q->dq_pass2.p,
+                       (const DevSeg*)q->dsegs.p, (const LmSegPlan*)q->dplans.p, none, st));
   q->leap_searched = false;  // (the neighbour searches of the listed E docs run when the statistics are asked for)
   return PA_OK;
 }
@@ -498,6 +518,16 @@ int pa_query_set_accumulator_buffer(pa_query* q, void* device_buffer, uint64_t b
     }
   };
   relocate(q->hq);
+  if (q->is_trow) {
+    for (int a = 0; a < q->hq.num_aggs; ++a)
+      if (q->trow_form[a] == 2) q->htrow.agg[a].time = (int64_t*)q->sections[q->trow_time_section[a]].ptr;
+    PA_HIP(hipMemcpy(q->trow_desc.p, &q->htrow, sizeof(TrowDesc), hipMemcpyHostToDevice));
+    if (q->trow_wide) {
+      DevQuery h2 = q->hq;
+      h2.trow_pass = 2;
+      PA_HIP(hipMemcpy(q->dq_pass2.p, &h2, sizeof(DevQuery), hipMemcpyHostToDevice));
+    }
+  }
   if (q->is_filtered) {
     q->hfilt.lane_count = (unsigned long long*)q->sections[q->lane_section].ptr;
     PA_HIP(hipMemcpy(q->filt_desc.p, &q->hfilt, sizeof(FiltDesc), hipMemcpyHostToDevice));
@@ -571,6 +601,11 @@ int pa_query_plan(const pa_query* q, int32_t* strategy, int32_t* steps, int32_t*
 }
 
 int32_t pa_query_num_eager_literals(const pa_query* q) { return q && q->prepared ? q->num_eager : -1; }
+
+int32_t pa_query_time_row_form(const pa_query* q, int32_t agg) {
+  if (!q || !q->prepared || agg < 0 || agg >= q->spec.num_aggs) return -1;
+  return q->trow_form[agg];
+}
 
 int32_t pa_query_lane_major(const pa_query* q) { return q && q->prepared ? q->lane_major : -1; }
 int32_t pa_query_eq_prefilter(const pa_query* q) { return q && q->prepared ? q->eq_prefilter : -1; }

@@ -127,6 +127,7 @@ __global__ void __launch_bounds__(256) compact_final_kernel(const unsigned long 
     for (int a = 0; a < d.nagg; ++a) {
       const int t = d.type[a];
       if (t == PA_AGG_VALUE_HISTOGRAM) continue;  // 0 bytes per row (pa_query_fetch_histogram reads the bins)
+      if (is_trow_agg(t)) continue;               // 0 bytes per row (pa_query_fetch_time_rows reads the rows)
       if (t == PA_AGG_DISTINCTCOUNTHLL || t == PA_AGG_DISTINCTCOUNT) {
         const int64_t per = d.per[a];  // (a multiple of 16 bytes)
         const u32x4* src = (const u32x4*)((const uint8_t*)d.sec[a] + k * per);

@@ -68,14 +68,22 @@ enum Strategy : int32_t {
   // transform expressions (SUM(ADD(a, b)), GROUP BY timeConvert(...)): filter + one gather of the operand columns + the
   // expression programs per matching doc (pa_strat_expr.h "expressions"): workgroup-private accumulators in LDS over a direct
   // key space, flushed once per workgroup, or device-scope atomics (direct or hashed key space)
-  STRAT_EXPR_LDS = 133, STRAT_EXPR = 134
+  STRAT_EXPR_LDS = 133, STRAT_EXPR = 134,
+  // FIRSTWITHTIME / LASTWITHTIME (PA_AGG_*_ROW_BY_TIME): filter + per group a 64-bit max of a synthesized (time, row)
+  // word next to the ordinary aggregations (pa_strat_trow.h "row by time"): workgroup-private accumulators in LDS,
+  // flushed once per workgroup, or device-scope atomics; the wide form launches the scan twice (DevQuery::trow_pass)
+  STRAT_TROW_LDS = 135, STRAT_TROW = 136
 };
+__host__ __device__ constexpr bool is_trow(int s) { return s == STRAT_TROW_LDS || s == STRAT_TROW; }
+__host__ __device__ constexpr bool is_trow_agg(int type) {
+  return type == PA_AGG_LAST_ROW_BY_TIME || type == PA_AGG_FIRST_ROW_BY_TIME;
+}
 __host__ __device__ constexpr bool is_distinct(int s) { return s == STRAT_DISTINCT_LDS || s == STRAT_DISTINCT; }
 __host__ __device__ constexpr bool is_filtered(int s) { return s == STRAT_FILTERED_LDS || s == STRAT_FILTERED; }
 // strategies whose accumulators (Acc<STRAT>) are the workgroup's LDS copies
 __host__ __device__ constexpr bool is_expr(int s) { return s == STRAT_EXPR_LDS || s == STRAT_EXPR; }
 __host__ __device__ constexpr bool acc_in_lds(int s) {
-  return s == STRAT_LDS || s == STRAT_FILTERED_LDS || s == STRAT_EXPR_LDS;
+  return s == STRAT_LDS || s == STRAT_FILTERED_LDS || s == STRAT_EXPR_LDS || s == STRAT_TROW_LDS;
 }
 __host__ __device__ constexpr bool is_pcount(int s) { return s == STRAT_PCOUNT || s == STRAT_PCOUNT_MV; }
 // STRAT_GDENSE: 4-wave workgroups; STRAT_GDENSE8 / STRAT_GDENSE12: the same kernel with 8- / 12-wave workgroups (2 / 3
@@ -348,6 +356,30 @@ struct DevQuery {
   uint32_t* keybits;             // distinct: the key-presence bitmap (PA_ACC_KEYBITS_U32), (num_keys + 31) / 32 words
   const struct FiltDesc* filt;   // filtered aggregations: the lanes' descriptor (nullptr otherwise)
   const struct ExprDesc* expr;   // transform expressions: the programs' descriptor (nullptr otherwise)
+  // row by time (STRAT_TROW*): the words' layout (nullptr otherwise), and which launch this descriptor drives,
+  // wave-uniform: 0 = the only launch (every such aggregation packed), 1 = the first launch of two (wide aggregations
+  // keep their time word), 2 = the second: only the wide aggregations' row words accumulate — no COUNT, no other
+  // aggregation, no numDocsScanned (the planner gives such a query no fused filter statistics)
+  const struct TrowDesc* trow;
+  int32_t trow_pass, pad_trow;
+};
+// ---------------------------------------------------------------- row by time (STRAT_TROW_LDS / STRAT_TROW)
+// PA_AGG_LAST / FIRST_ROW_BY_TIME aggregation a (pa_strat_trow.h "row by time"). x = the doc's time: the raw INT / LONG
+// value, or the table-wide value id of a dictionary time column (ids in value order); row = segment bind index <<
+// doc_bits | docId.
+//   packed  word = ((x - tmin) ^ flip) << row_bits | row + 1 into DevAgg::acc_i64 (0 = no row); flip = all ones inside the
+//           time width for FIRST, 0 for LAST; the word stays below 2^63
+//   wide    launch 1: max of x ^ flip into `time` (flip = all 64 ones for FIRST; identity INT64_MIN); launch 2: max of
+//           row + 1 over the docs whose x ^ flip equals time[key] into DevAgg::acc_i64
+struct TrowAgg {
+  int64_t tmin;
+  uint64_t flip;
+  int64_t* time;
+  int32_t row_bits, doc_bits;
+  int32_t wide, pad;
+};
+struct TrowDesc {
+  TrowAgg agg[PA_MAX_AGGS];
 };
 // ---------------------------------------------------------------- transform expressions (STRAT_EXPR_LDS / STRAT_EXPR)
 // The validated programs of pa_query_set_expressions (pinot_amd.h "transform expressions"), wave-uniform: the scan reads

@@ -94,6 +94,8 @@ struct Column {
   int32_t max_values = 1;   // MV: most values in one row
   bool fits_int32 = false;  // every value (dictionary or raw, INT/LONG) fits in int32
   bool dict_sorted = false; // dictionary values strictly ascending (COLF_DICT_SORTED)
+  bool has_raw_minmax = false;  // raw INT / LONG column with docs: raw_min / raw_max hold its smallest / largest value
+  int64_t raw_min = 0, raw_max = 0;
   std::vector<uint64_t> hvals;  // host copy of the dictionary values (8-byte bits): table-wide value dictionaries
   uint64_t dict_hash = 0;       // FNV-1a of hvals: identical dictionaries across segments are found without a compare
   DevBuf words;   // guard + stream + pad (SV dict)
@@ -200,6 +202,8 @@ inline int64_t presence_stride(const pa_agg_spec& A) { return (A.num_values + 15
 inline int64_t hist_stride(const pa_agg_spec& A) { return (A.num_values + 1) & ~int64_t(1); }
 // DISTINCTCOUNT and VALUE_HISTOGRAM index their accumulators by the column's table-wide value id
 inline bool value_id_agg(int32_t type) { return type == PA_AGG_DISTINCTCOUNT || type == PA_AGG_VALUE_HISTOGRAM; }
+// FIRSTWITHTIME / LASTWITHTIME: the per-group winning row (pa_strat_trow.h)
+inline bool time_row_agg(int32_t type) { return type == PA_AGG_LAST_ROW_BY_TIME || type == PA_AGG_FIRST_ROW_BY_TIME; }
 // element bytes of an accumulator section
 inline size_t section_es(int32_t kind) {
   return (kind == PA_ACC_HLL_U8 || kind == PA_ACC_PRESENCE_U8) ? 1 : (kind == PA_ACC_KEYBITS_U32 ? 4 : 8);
@@ -353,8 +357,23 @@ struct pa_query {
   pa_expr_spec expr_spec{};
   ExprDesc hexpr{};
   DevBuf expr_desc;
+  // FIRSTWITHTIME / LASTWITHTIME (PA_AGG_*_ROW_BY_TIME; pa_strat_trow.h "row by time"): per aggregation its form (0 = not
+  // such an aggregation, 1 = packed, 2 = wide), the bits of its word's row field and the wide form's time section; the
+  // descriptor of the wide form's second launch (hq with trow_pass = 2) and the finish kernel's buffers
+  bool is_trow = false;
+  bool trow_wide = false;  // some aggregation takes the wide form: pa_query_scan launches the scan twice
+  int trow_form[PA_MAX_AGGS] = {0};
+  int trow_row_bits[PA_MAX_AGGS] = {0}, trow_doc_bits[PA_MAX_AGGS] = {0};
+  int trow_time_section[PA_MAX_AGGS] = {0};
+  int trow_tbits[PA_MAX_AGGS] = {0};        // packed: bits of the time key
+  int64_t trow_tmin[PA_MAX_AGGS] = {0};     // packed, raw time column: the bound segments' smallest time
+  TrowDesc htrow{};
+  DevBuf dq_pass2, trow_desc, trow_buf;
 
   ~pa_query() {
+    dev_free(dq_pass2);
+    dev_free(trow_desc);
+    dev_free(trow_buf);
     dev_free(expr_desc);
     dev_free(filt_desc);
     dev_free(filt_leaves);
@@ -471,6 +490,8 @@ int filtered_plan(pa_query* q, const Prep& P);      // prepare, after fill_devqu
 int expr_check_spec(const pa_query_spec& s, const pa_expr_spec& e);  // pa_query_set_expressions: the programs' validation
 int expr_validate(pa_query* q, Prep& P);            // prepare, after build_segments: what an expression query refuses
 int expr_plan(pa_query* q, const Prep& P);          // prepare, after fill_devquery: the programs' descriptor, uploaded
+int trow_validate(pa_query* q, Prep& P);            // prepare, after build_segments: what a row-by-time query refuses
+int trow_plan(pa_query* q);                         // prepare, after fill_devquery: the words' layout; the second descriptor
 int mv_group_component(const pa_query* q);
 int plan_filter(pa_query* q, Prep& P);
 int plan_slots(pa_query* q, Prep& P);

@@ -202,10 +202,12 @@ int plan_slots(pa_query* q, Prep& P) {
     P.slot_gb[P.gb_slot[j]] = 1;
   }
   P.agg_slot.assign(s.num_aggs, 0);
+  q->is_trow = false;
   for (int a = 0; a < s.num_aggs; ++a) {
     const int t = s.aggs[a].type;
-    if (t < PA_AGG_COUNT || t > PA_AGG_VALUE_HISTOGRAM) return fail(PA_EINVAL, "bad aggregation type");
+    if (t < PA_AGG_COUNT || t > PA_AGG_FIRST_ROW_BY_TIME) return fail(PA_EINVAL, "bad aggregation type");
     if (t == PA_AGG_COUNT) continue;
+    if (time_row_agg(t)) q->is_trow = true;
     P.agg_slot[a] = slot_of(q, s.aggs[a].column_id);
     if (P.agg_slot[a] < 0) return fail(PA_EUNSUPPORTED, "too many distinct columns in one query");
     if (t == PA_AGG_DISTINCTCOUNTHLL && (s.aggs[a].log2m < 4 || s.aggs[a].log2m > 16))
@@ -971,6 +973,24 @@ int build_segments(pa_query* q, Prep& P) {
         P.agg_src[a] = SRC_INT;
         continue;
       }
+      if (time_row_agg(A.type)) {
+        // the time column (trow_validate checks its kind and type): a dictionary column's ids go through the value
+        // remap into the table-wide dictionary, whose ids follow the order of the values
+        if (c->kind == COL_SV_DICT) {
+          const std::vector<int32_t>& rm = q->vremaps[si][a];
+          if (!rm.empty()) {
+            void* dp = nullptr;
+            rc = upload_owned(q, rm.data(), rm.size() * 4, &dp);
+            if (rc) return rc;
+            d.hll_lut[a] = (const uint32_t*)dp;
+          } else if (c->cardinality > A.num_values) {
+            return fail(PA_EINVAL, "segment dictionary larger than the time column's value space without a remap");
+          }
+        }
+        P.agg_src[a] = SRC_LONG;
+        P.val_fast[a] = 0;
+        continue;
+      }
       if (value_id_agg(A.type)) {
         const bool hist = A.type == PA_AGG_VALUE_HISTOGRAM;
         if (c->kind != COL_SV_DICT && c->kind != COL_MV_DICT)
@@ -1059,6 +1079,16 @@ int plan_accumulators(pa_query* q, Prep& P) {
                                        "group-by cardinalities too large to address directly) is not supported");
         if (K > INT64_MAX / 8 / hist_stride(A)) return fail(PA_ENOMEM, "VALUE_HISTOGRAM: keys x values too large");
         sec.push_back({PA_ACC_HIST_U64, K * hist_stride(A)});
+        break;
+      case PA_AGG_LAST_ROW_BY_TIME:
+      case PA_AGG_FIRST_ROW_BY_TIME:
+        // (wide form: the time word's section first, then the row word's, which is the aggregation's section)
+        q->trow_time_section[a] = -1;
+        if (q->trow_form[a] == 2) {
+          sec.push_back({PA_ACC_TIME_MAX_I64, K});
+          q->trow_time_section[a] = (int)sec.size() - 1;
+        }
+        sec.push_back({PA_ACC_TIME_ROW_U64, K});
         break;
     }
     q->agg_section[a] = (int)sec.size() - 1;
@@ -1238,6 +1268,119 @@ int expr_plan(pa_query* q, const Prep& P) {
   if (rc) return rc;
   PA_HIP(hipMemcpy(q->expr_desc.p, &E, sizeof(E), hipMemcpyHostToDevice));
   q->hq.expr = (const ExprDesc*)q->expr_desc.p;
+  return PA_OK;
+}
+
+// A query with PA_AGG_LAST / FIRST_ROW_BY_TIME aggregations against what the row-by-time strategies cover
+// (pa_strat_trow.h "row by time"), and the form of every such aggregation's word: the row field holds (segment bind
+// index << doc bits | docId) + 1; the packed form puts the time key above it when both fit 63 bits.
+static int bit_length(uint64_t x) { return x == 0 ? 0 : 64 - __builtin_clzll(x); }
+int trow_validate(pa_query* q, Prep& P) {
+  const pa_query_spec& s = q->spec;
+  for (int a = 0; a < PA_MAX_AGGS; ++a) q->trow_form[a] = 0;
+  q->trow_wide = false;
+  if (q->is_select || q->is_distinct) q->is_trow = false;  // (their spec's aggregations are not computed)
+  if (!q->is_trow) return PA_OK;
+  if (q->is_filtered)
+    return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME in a query with aggregation filters is not supported");
+  if (q->is_expr)
+    return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME next to transform expressions is not supported");
+  if (q->hashed)
+    return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME over a hashed key space (a raw group-by column, or a product "
+                                 "of group-by cardinalities too large to address directly) is not supported");
+  if (q->limit_mode)
+    return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME where numGroupsLimit trimming runs its first-position + sort "
+                                 "passes is not supported (the prefix walk is)");
+  if (q->has_mv || P.gb_mv)
+    return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME next to a multi-value group-by or aggregation column is not "
+                                 "supported");
+  int64_t maxdocs = 1;
+  for (int si = 0; si < q->nseg; ++si) maxdocs = std::max<int64_t>(maxdocs, q->segs[si]->num_docs);
+  const int doc_bits = std::max(1, bit_length((uint64_t)(maxdocs - 1)));
+  const uint64_t max_row = ((uint64_t)std::max(0, q->nseg - 1) << doc_bits) | (uint64_t)(maxdocs - 1);
+  const int row_bits = bit_length(max_row + 1);
+  for (int a = 0; a < s.num_aggs; ++a) {
+    const pa_agg_spec& A = s.aggs[a];
+    if (!time_row_agg(A.type)) continue;
+    int kind = COL_NONE;
+    bool any = false;
+    int64_t tmin = 0, tmax = 0;
+    for (int si = 0; si < q->nseg; ++si) {
+      auto it = q->segs[si]->cols.find(A.column_id);
+      if (it == q->segs[si]->cols.end()) return fail(PA_EINVAL, "time column missing in a segment");
+      const Column* c = it->second;
+      if (c->kind != COL_SV_DICT && c->kind != COL_SV_RAW)
+        return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: a multi-value time column is not supported");
+      if (c->vtype != PA_INT && c->vtype != PA_LONG)
+        return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: the time column must be INT or LONG");
+      if (si == 0) kind = c->kind;
+      if (c->kind != kind)
+        return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: the time column is dictionary-encoded in some bound "
+                                     "segments only");
+      if (c->kind == COL_SV_RAW && c->has_raw_minmax) {
+        tmin = any ? std::min(tmin, c->raw_min) : c->raw_min;
+        tmax = any ? std::max(tmax, c->raw_max) : c->raw_max;
+        any = true;
+      }
+    }
+    q->trow_row_bits[a] = row_bits;
+    q->trow_doc_bits[a] = doc_bits;
+    q->trow_tmin[a] = 0;
+    if (kind == COL_SV_RAW) {
+      const int tbits = bit_length((uint64_t)tmax - (uint64_t)tmin);
+      const bool fits = tbits + row_bits <= 63;
+      if (q->tune.time_rows_wide == 0 && !fits)
+        return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: the time range does not fit the packed form");
+      q->trow_form[a] = (q->tune.time_rows_wide == 1 || !fits) ? 2 : 1;
+      q->trow_tbits[a] = tbits;
+      q->trow_tmin[a] = tmin;
+    } else {
+      if (A.num_values < 1 || A.num_values > INT32_MAX)
+        return fail(PA_EINVAL, "a dictionary time column needs the table-wide value count (1..2^31-1)");
+      const int tbits = bit_length((uint64_t)(A.num_values - 1));
+      if (tbits + row_bits > 63)
+        return fail(PA_EUNSUPPORTED, "FIRSTWITHTIME / LASTWITHTIME: dictionary ids and rows do not fit 63 bits together");
+      q->trow_form[a] = 1;
+      q->trow_tbits[a] = tbits;
+    }
+    if (q->trow_form[a] == 2) {
+      q->trow_wide = true;
+      q->trow_row_bits[a] = 63;
+    }
+  }
+  return PA_OK;
+}
+
+// The words' layout, uploaded (after fill_devquery: the sections exist), and which launch hq drives.
+int trow_plan(pa_query* q) {
+  const pa_query_spec& s = q->spec;
+  TrowDesc& T = q->htrow;
+  std::memset(&T, 0, sizeof(T));
+  for (int a = 0; a < s.num_aggs; ++a) {
+    if (!q->trow_form[a]) continue;
+    TrowAgg& t = T.agg[a];
+    const bool first = s.aggs[a].type == PA_AGG_FIRST_ROW_BY_TIME;
+    t.wide = q->trow_form[a] == 2;
+    t.doc_bits = q->trow_doc_bits[a];
+    if (t.wide) {
+      t.tmin = 0;
+      t.flip = first ? ~uint64_t(0) : 0;
+      t.row_bits = 0;
+      t.time = (int64_t*)q->sections[q->trow_time_section[a]].ptr;
+    } else {
+      t.tmin = q->trow_tmin[a];
+      t.flip = first ? ((uint64_t(1) << q->trow_tbits[a]) - 1) : 0;
+      t.row_bits = q->trow_row_bits[a];
+      t.time = nullptr;
+    }
+  }
+  if (!q->trow_desc.p) {
+    int rc = dev_alloc(q->trow_desc, sizeof(TrowDesc));
+    if (rc) return rc;
+  }
+  PA_HIP(hipMemcpy(q->trow_desc.p, &T, sizeof(T), hipMemcpyHostToDevice));
+  q->hq.trow = (const TrowDesc*)q->trow_desc.p;
+  q->hq.trow_pass = q->trow_wide ? 1 : 0;
   return PA_OK;
 }
 

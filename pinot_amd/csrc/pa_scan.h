@@ -1352,6 +1352,15 @@ template <int STRAT>
 __device__ __forceinline__ void expr_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
                                           const uint32_t* img, int doc_local, int64_t doc, uint64_t matched, int lane,
                                           const Acc<STRAT>& acc);
+// pa_strat_trow.h
+template <int STRAT>
+__device__ __forceinline__ void trow_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                          const uint32_t* img, int doc_local, int64_t doc, uint64_t matched, int lane,
+                                          const Acc<STRAT>& acc);
+template <int WGS>
+__device__ __forceinline__ void trow_lds_zero(const DevQuery* q, unsigned char* lds_acc);
+template <int WGS>
+__device__ __forceinline__ void trow_lds_flush(const DevQuery* q, unsigned char* lds_acc);
 // pa_strat_part.h
 template <int STRAT, int STEPS, int LM>
 __device__ __forceinline__ void part_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
@@ -1424,6 +1433,13 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
       const uint64_t sm = __ballot((m >> i) & 1u);
       if (sm == 0) continue;
       expr_step<STRAT>(q, seg, img, i * kWave + lane, doc_base + i * kWave + lane, sm, lane, acc);
+    }
+  } else if constexpr (is_trow(STRAT)) {
+    static_assert(!LM, "row-by-time queries run step-major tiles");
+    for (int i = 0; i < STEPS; ++i) {
+      const uint64_t sm = __ballot((m >> i) & 1u);
+      if (sm == 0) continue;
+      trow_step<STRAT>(q, seg, img, i * kWave + lane, doc_base + i * kWave + lane, sm, lane, acc);
     }
   } else if constexpr (is_lane(STRAT)) {
     if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_tile<LM, STEPS, STRAT>(q, seg, img, doc_base, m, lane, la, lds);
@@ -1758,6 +1774,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_EXPR_LDS) lds_acc_zero<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_TROW_LDS) trow_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_zero<WGS>(q, lds_acc);
   const int64_t T = q->total_wtiles;
   const int64_t W = (int64_t)gridDim.x * WPW;
@@ -1914,6 +1931,10 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (STRAT == STRAT_DISTINCT_LDS) distinct_lds_flush<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_flush<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_EXPR_LDS) lds_acc_flush<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_TROW_LDS) trow_lds_flush<WGS>(q, lds_acc);
+  if constexpr (is_trow(STRAT)) {  // (the wide form's second launch sees the docs the first counted)
+    if (q->trow_pass == 2) matched = 0;
+  }
   if (!is_pemit(STRAT)) {  // (the partitioned count pass counts numDocsScanned; its emit pass sees the same docs)
     const int64_t wm = wave_sum_i64((int64_t)matched);
     if (lane == 0 && wm != 0) __hip_atomic_fetch_add(gp(q->matched_docs), (unsigned long long)wm, RLX);

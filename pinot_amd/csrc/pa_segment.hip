@@ -206,6 +206,17 @@ int pa_segment_add_raw_column(pa_segment* seg, int32_t column_id, int32_t value_
     for (int32_t i = 0; i < seg->num_docs; ++i) fits &= v[i] >= INT32_MIN && v[i] <= INT32_MAX;
     c->fits_int32 = fits;
   }
+  if ((value_type == PA_INT || value_type == PA_LONG) && seg->num_docs > 0) {  // (column metadata min/max, INT / LONG)
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    for (int32_t i = 0; i < seg->num_docs; ++i) {
+      const int64_t x = value_type == PA_INT ? (int64_t)((const int32_t*)values)[i] : ((const int64_t*)values)[i];
+      lo = x < lo ? x : lo;
+      hi = x > hi ? x : hi;
+    }
+    c->raw_min = lo;
+    c->raw_max = hi;
+    c->has_raw_minmax = true;
+  }
   seg->bytes += c->raw.n;
   seg->cols[column_id] = c;
   return PA_OK;

@@ -81,8 +81,19 @@ __global__ void __launch_bounds__(kSelFinishThreads) select_finish_kernel(const 
   if (tid == 0) *gp(S->result_n) = (uint32_t)R;
 }
 
-// Output cell (row r, column c): the segment's dictId of a dictionary column (bit-unpacked at (segment, doc)), the
-// value of a raw column (FLOAT widened: the cell holds the bits of a double).
+// One cell: the segment's dictId of a dictionary column (bit-unpacked at `doc`), the value of a raw column (FLOAT
+// widened: the cell holds the bits of a double). Shared by the selection's cells and the row-by-time finish.
+__device__ __forceinline__ int64_t sel_read_cell(const SelCol& col, int64_t doc) {
+  if (col.kind == COL_SV_DICT) return (int64_t)decode_global(col.words, doc, col.nbits);
+  switch (col.vtype) {
+    case PA_INT: return (int64_t)gp((const int32_t*)col.raw)[doc];
+    case PA_LONG: return gp((const int64_t*)col.raw)[doc];
+    case PA_FLOAT: return __builtin_bit_cast(int64_t, (double)gp((const float*)col.raw)[doc]);
+    default: return gp((const int64_t*)col.raw)[doc];
+  }
+}
+
+// Output cell (row r, column c) at (segment, doc) of the sorted result.
 __global__ void __launch_bounds__(kSelGatherThreads) select_cells_kernel(const SelDesc* __restrict__ S) {
   const uint64_t R = *gp(S->result_n);
   const uint64_t nout = (uint64_t)S->nout, K = (uint64_t)S->K;
@@ -93,18 +104,34 @@ __global__ void __launch_bounds__(kSelGatherThreads) select_cells_kernel(const S
     const uint64_t seg = v.y >> 32;
     const int64_t doc = (int64_t)(v.y & 0xffffffffull);
     const SelCol col = S->out_cols[seg * nout + c];
-    int64_t cell;
-    if (col.kind == COL_SV_DICT) {
-      cell = (int64_t)decode_global(col.words, doc, col.nbits);
-    } else {
-      switch (col.vtype) {
-        case PA_INT: cell = (int64_t)gp((const int32_t*)col.raw)[doc]; break;
-        case PA_LONG: cell = gp((const int64_t*)col.raw)[doc]; break;
-        case PA_FLOAT: cell = __builtin_bit_cast(int64_t, (double)gp((const float*)col.raw)[doc]); break;
-        default: cell = gp((const int64_t*)col.raw)[doc]; break;
-      }
+    gp(S->cells)[c * K + r] = sel_read_cell(col, doc);
+  }
+}
+
+// FIRSTWITHTIME / LASTWITHTIME finish (pa_query_fetch_time_rows): one thread per (group, column) over the compacted
+// group order of pa_query_fetch. words[keys[g]] & row_mask = row + 1 of group g's winning doc (0: no row), row = segment
+// bind index << doc_bits | docId; the thread of column 0 also writes the row's (segment, doc). Cell c of group g goes
+// to cells[c * n + g] (0 for a group with no row).
+__global__ void __launch_bounds__(kSelGatherThreads)
+    time_rows_kernel(const uint64_t* __restrict__ words, const int64_t* __restrict__ keys, int64_t n, int ncol,
+                     uint64_t row_mask, int doc_bits, int nseg, const SelCol* __restrict__ cols, int32_t* __restrict__ out_seg,
+                     int32_t* __restrict__ out_doc, int64_t* __restrict__ cells) {
+  const int64_t per = ncol > 0 ? ncol : 1;
+  for (int64_t idx = (int64_t)blockIdx.x * kSelGatherThreads + threadIdx.x; idx < n * per;
+       idx += (int64_t)gridDim.x * kSelGatherThreads) {
+    const int64_t c = idx / n, g = idx % n;
+    const uint64_t r1 = gp(words)[gp(keys)[g]] & row_mask;
+    int64_t seg = -1, doc = -1;
+    if (r1 != 0) {
+      seg = (int64_t)((r1 - 1) >> doc_bits);
+      doc = (int64_t)((r1 - 1) & ((1ull << doc_bits) - 1ull));
     }
-    gp(S->cells)[c * K + r] = cell;
+    if (seg >= nseg) seg = doc = -1;  // (cannot happen: the scan builds rows of bound segments only)
+    if (c == 0) {
+      gp(out_seg)[g] = (int32_t)seg;
+      gp(out_doc)[g] = (int32_t)doc;
+    }
+    if (ncol > 0) gp(cells)[c * n + g] = seg >= 0 ? sel_read_cell(cols[seg * ncol + c], doc) : 0;
   }
 }
 
@@ -131,6 +158,17 @@ static int select_check_column(const pa_query* q, int32_t cid, bool want_raw, bo
       return fail(PA_EUNSUPPORTED, "selection: raw " + name + " of a type without an order");
   }
   return PA_OK;
+}
+
+// A column of one segment as the finish kernels read its cells (no remap, not staged).
+static void select_describe(const Column* c, SelCol& o) {
+  o.words = c->words.p ? (const uint32_t*)c->words.p + kGuardWords : nullptr;
+  o.raw = c->raw.p;
+  o.remap = nullptr;
+  o.kind = c->kind;
+  o.nbits = c->nbits;
+  o.vtype = c->vtype;
+  o.lds_off = -1;
 }
 
 int select_validate(pa_query* q) {
@@ -207,13 +245,7 @@ int select_plan(pa_query* q) {
 
   auto describe = [&](int si, int32_t cid, const std::vector<int32_t>* remap, SelCol& o) -> int {
     const Column* c = select_column(q, si, cid);
-    o.words = c->words.p ? (const uint32_t*)c->words.p + kGuardWords : nullptr;
-    o.raw = c->raw.p;
-    o.remap = nullptr;
-    o.kind = c->kind;
-    o.nbits = c->nbits;
-    o.vtype = c->vtype;
-    o.lds_off = -1;
+    select_describe(c, o);
     if (remap && !remap->empty()) {
       void* p = nullptr;
       if (int rc = upload_owned(q, remap->data(), remap->size() * sizeof(int32_t), &p)) return rc;
@@ -366,6 +398,73 @@ int64_t pa_query_fetch_selection(pa_query* q, void* stream, int64_t capacity, in
     }
   }
   return R;
+}
+
+int pa_query_fetch_time_rows(pa_query* q, void* stream, int32_t agg, int64_t num_groups, int32_t num_columns,
+                             const int32_t* columns, int32_t* out_segments, int32_t* out_docs, int64_t* const* out_cells) {
+  if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
+  if (const char* t = tuning_invalidating(q->tune))
+    return fail(PA_EINVAL, std::string("results invalid: tuning ") + t + " is set");
+  if (agg < 0 || agg >= q->spec.num_aggs || !q->trow_form[agg])
+    return fail(PA_EINVAL, "not a LAST / FIRST_ROW_BY_TIME aggregation");
+  if (q->hashed || q->agg_section[agg] < 0) return fail(PA_EINVAL, "internal: time rows without a direct key space");
+  if (num_groups < 0 || num_groups > INT32_MAX || num_columns < 0 || num_columns > PA_MAX_SELECT_COLUMNS ||
+      (num_columns > 0 && !columns))
+    return fail(PA_EINVAL, "fetch time rows: bad sizes");
+  for (int c = 0; c < num_columns; ++c)
+    if (int rc = select_check_column(q, columns[c], false, false, "row-by-time")) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the keys pa_query_fetch returns for these accumulators: the same compaction passes
+  const int64_t K = q->num_keys;
+  const int64_t nb = (K + 2047) / 2048;
+  if ((int64_t)q->fetch_blocks.n < (nb + 1) * 4) {
+    dev_free(q->fetch_blocks);
+    if (int rc = dev_alloc(q->fetch_blocks, (size_t)(nb + 1) * 4)) return rc;
+  }
+  const int all = q->spec.num_group_by != 0 ? 0 : 1;
+  const unsigned long long* count = (const unsigned long long*)q->sections[0].ptr;
+  uint32_t total = 0;
+  PA_HIP(launch_compact(count, K, all, (uint32_t*)q->fetch_blocks.p, 0, nullptr, 0, st));
+  PA_HIP(hipMemcpyAsync(&total, (uint32_t*)q->fetch_blocks.p + nb, 4, hipMemcpyDeviceToHost, st));
+  PA_HIP(hipStreamSynchronize(st));
+  if ((int64_t)total != num_groups)
+    return fail(PA_EINVAL, "num_groups is not the group count pa_query_fetch returns for these accumulators");
+  if (num_groups == 0) return PA_OK;
+  // keys | segments | docs | cells [column][group] | column descriptors [segment][column]
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t n = (size_t)num_groups, nc = (size_t)num_columns;
+  const size_t o_seg = al(n * 8), o_doc = o_seg + al(n * 4), o_cells = o_doc + al(n * 4);
+  const size_t o_cols = o_cells + al(n * nc * 8);
+  const size_t bytes = o_cols + al((size_t)q->nseg * nc * sizeof(SelCol));
+  if (q->trow_buf.n < bytes || !q->trow_buf.p) {
+    dev_free(q->trow_buf);
+    if (int rc = dev_alloc(q->trow_buf, bytes)) return rc;
+  }
+  char* b = (char*)q->trow_buf.p;
+  std::vector<SelCol> cols((size_t)q->nseg * nc);
+  for (int si = 0; si < q->nseg; ++si)
+    for (size_t c = 0; c < nc; ++c) select_describe(select_column(q, si, columns[c]), cols[(size_t)si * nc + c]);
+  if (!cols.empty()) PA_HIP(hipMemcpy(b + o_cols, cols.data(), cols.size() * sizeof(SelCol), hipMemcpyHostToDevice));
+  CompactDesc d;
+  std::memset(&d, 0, sizeof(d));
+  d.keys = (int64_t*)b;
+  PA_HIP(launch_compact(count, K, all, (uint32_t*)q->fetch_blocks.p, num_groups, &d, 1, st));
+  const int row_bits = q->trow_row_bits[agg];
+  const uint64_t row_mask = (uint64_t(1) << row_bits) - 1;
+  const int64_t threads = num_groups * std::max<int64_t>(1, num_columns);
+  hipLaunchKernelGGL(time_rows_kernel,
+                     dim3((unsigned)std::min<int64_t>(1024, (threads + kSelGatherThreads - 1) / kSelGatherThreads)),
+                     dim3(kSelGatherThreads), 0, st, (const uint64_t*)q->sections[q->agg_section[agg]].ptr,
+                     (const int64_t*)b, num_groups, (int)num_columns, row_mask, q->trow_doc_bits[agg], q->nseg,
+                     (const SelCol*)(b + o_cols), (int32_t*)(b + o_seg), (int32_t*)(b + o_doc), (int64_t*)(b + o_cells));
+  PA_HIP(hipGetLastError());
+  if (out_segments) PA_HIP(hipMemcpyAsync(out_segments, b + o_seg, n * 4, hipMemcpyDeviceToHost, st));
+  if (out_docs) PA_HIP(hipMemcpyAsync(out_docs, b + o_doc, n * 4, hipMemcpyDeviceToHost, st));
+  for (size_t c = 0; c < nc; ++c)
+    if (out_cells && out_cells[c])
+      PA_HIP(hipMemcpyAsync(out_cells[c], b + o_cells + c * n * 8, n * 8, hipMemcpyDeviceToHost, st));
+  PA_HIP(hipStreamSynchronize(st));
+  return PA_OK;
 }
 
 int pa_query_selection_segment_docs(const pa_query* q, int64_t* out) {

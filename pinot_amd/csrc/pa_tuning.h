@@ -82,7 +82,15 @@
   X(expr_lds, -1, 0, 1, 0)                                                                                             \
   /* hashed key spaces: the slot table holds at most this many slots (rounded down to a power of two; default: twice   \
      the keys that can exist, up to 2^28). A small cap lets a small table reach the group-key table overflow report */  \
-  X(hash_slots_cap, -1, 1024, 1 << 28, 0)
+  X(hash_slots_cap, -1, 1024, 1 << 28, 0)                                                                              \
+  /* FIRSTWITHTIME / LASTWITHTIME: 1 = the wide form (two scan launches) for every raw time column, 0 = the packed     \
+     form, refused at prepare where the time range does not fit beside the row (default: packed wherever it fits). A     \
+     dictionary time column is always packed. Lets small tables reach the wide form */                                 \
+  X(time_rows_wide, -1, 0, 1, 0)                                                                                       \
+  /* FIRSTWITHTIME / LASTWITHTIME: 0 = device-scope atomics (STRAT_TROW), 1 = the workgroup-private LDS accumulators    \
+     (STRAT_TROW_LDS) whenever they fit next to a tile ring (default: when they take at most 64 KiB and the matching    \
+     docs are dense, STRAT_LDS's rule; PA_QF_FORCE_LDS / PA_QF_FORCE_GLOBAL act as on STRAT_LDS) */                    \
+  X(time_rows_lds, -1, 0, 1, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;

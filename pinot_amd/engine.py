@@ -118,6 +118,61 @@ class MinMaxRangePair:
     max: float
 
 
+@dataclass
+class ValueTimePair:
+    """FirstWithTime / LastWithTimeAggregationFunction intermediate result (ValueLongPair: the winning doc's value in
+    the declared type — an int for 'BOOLEAN', as IntLongPair — and its time). The empty pair is the reference's
+    DEFAULT_VALUE_TIME_PAIR (with_time_default)."""
+    value: object
+    time: int
+
+    def __eq__(self, other):  # (NaN values of two default pairs compare equal)
+        if not isinstance(other, ValueTimePair) or self.time != other.time:
+            return False
+        a, b = self.value, other.value
+        return a == b or (isinstance(a, float) and isinstance(b, float) and a != a and b != b)
+
+
+LONG_MIN, LONG_MAX = -(1 << 63), (1 << 63) - 1
+INT_MIN, INT_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def with_time_default(function, data_type):
+    """DEFAULT_VALUE_TIME_PAIR of {First,Last}{Int,Long,Float,Double,String}ValueWithTimeAggregationFunction: the value
+    Integer.MIN_VALUE / Long.MIN_VALUE / NaN / "", the time Long.MIN_VALUE for LAST and Long.MAX_VALUE for FIRST."""
+    value = {"BOOLEAN": INT_MIN, "INT": INT_MIN, "LONG": LONG_MIN, "FLOAT": float("nan"), "DOUBLE": float("nan"),
+             "STRING": ""}[data_type]
+    return ValueTimePair(value, LONG_MIN if function == "LASTWITHTIME" else LONG_MAX)
+
+
+def java_cast(value, stored_type, declared_type):
+    """A stored value read through the BlockValSet getter of the declared type (getIntValuesSV / getLongValuesSV /
+    getFloatValuesSV / getDoubleValuesSV over an INT / LONG / FLOAT / DOUBLE column): Java's primitive casts. long -> int
+    keeps the low 32 bits; float / double -> int / long saturates, NaN -> 0; 'BOOLEAN' reads the int."""
+    if declared_type == "STRING":
+        if stored_type != "STRING":
+            raise UnsupportedQuery("'STRING' over the %s column" % stored_type)
+        return str(value)
+    if stored_type not in ("INT", "LONG", "FLOAT", "DOUBLE"):
+        raise UnsupportedQuery("'%s' over the %s column" % (declared_type, stored_type))
+    floating = stored_type in ("FLOAT", "DOUBLE")
+    if declared_type in ("INT", "BOOLEAN", "LONG"):
+        lo, hi = (INT_MIN, INT_MAX) if declared_type != "LONG" else (LONG_MIN, LONG_MAX)
+        if floating:
+            x = float(value)
+            if x != x:
+                return 0
+            return hi if x >= hi else (lo if x <= lo else int(x))
+        v = int(value)
+        if declared_type != "LONG":
+            v = ((v + (1 << 31)) & 0xffffffff) - (1 << 31)
+        return v
+    if declared_type == "FLOAT":
+        with np.errstate(over="ignore"):  # (a double past Float.MAX_VALUE casts to infinity)
+            return float(np.float32(value))
+    return float(value)
+
+
 class ValueHistogram:
     """PercentileAggregationFunction / PercentileMVAggregationFunction intermediate result: the reference's
     DoubleArrayList of every aggregated value, held as a multiset: `values` float64 strictly ascending, `counts` int64
@@ -394,6 +449,15 @@ class GpuQueryExecutor:
                 else:
                     self.agg_map.append((acc_index((L.PA_AGG_MIN, cid, 0)), acc_index((L.PA_AGG_MAX, cid, 0))))
                 continue
+            if fn in Q.WITH_TIME_FUNCTIONS:
+                self._check_with_time(a)
+                self.agg_lane.append(-1)
+                cur[0] = -1
+                # keyed by (type, time column): the accumulator knows nothing of the value column, so aggregations
+                # over one time column share it
+                t = L.PA_AGG_LAST_ROW_BY_TIME if fn == "LASTWITHTIME" else L.PA_AGG_FIRST_ROW_BY_TIME
+                self.agg_map.append(acc_index((t, ids[a.time_column], 0)))
+                continue
             if fn.endswith("MV") and seg0.column(a.column).single_value:
                 raise UnsupportedQuery("%s on single-value column %s" % (fn, a.column))
             lane = lane_of(a)
@@ -452,7 +516,9 @@ class GpuQueryExecutor:
             spec.aggs[i].log2m = log2m
             if t == L.PA_AGG_SUM and names.get(cid) in self.wide_sum_columns:
                 spec.aggs[i].flags = L.PA_AGGF_WIDE_SUM
-            if t in (L.PA_AGG_DISTINCTCOUNT, L.PA_AGG_VALUE_HISTOGRAM):
+            time_dict = t in TIME_ROW_AGGS and self.segs[0].column(names[cid]).has_dictionary
+            if t in (L.PA_AGG_DISTINCTCOUNT, L.PA_AGG_VALUE_HISTOGRAM) or time_dict:
+                # (a dictionary time column of FIRSTWITHTIME / LASTWITHTIME: its table-wide dictionary, ids in value order)
                 name = names[cid]
                 if name in self.table_value_dicts:
                     vd = np.asarray(self.table_value_dicts[name])
@@ -626,8 +692,10 @@ class GpuQueryExecutor:
         try:
             L.check(lib.pa_query_prepare(self.handle), "pa_query_prepare")
         except L.PinotAmdError as e:
-            if (self.dev_filters or self.exprs) and getattr(e, "code", 0) == L.PA_EUNSUPPORTED:
-                # (what the library refuses of a query with aggregation filters or transform expressions)
+            with_time = any(a.function in Q.WITH_TIME_FUNCTIONS for a in q.aggregations)
+            if (self.dev_filters or self.exprs or with_time) and getattr(e, "code", 0) == L.PA_EUNSUPPORTED:
+                # (what the library refuses of a query with aggregation filters, transform expressions or
+                # FIRSTWITHTIME / LASTWITHTIME)
                 raise UnsupportedQuery(str(e)) from None
             raise
         self.num_keys = int(lib.pa_query_num_keys(self.handle))
@@ -641,6 +709,71 @@ class GpuQueryExecutor:
         for gd in self.global_dicts:
             self.strides.append(s)
             s *= len(gd) if gd is not None else 1
+
+    def _check_with_time(self, a):
+        """What FIRSTWITHTIME / LASTWITHTIME takes here (DESIGN.md "First / last with time", limits); the key-space
+        limits are the library's (pa_query_prepare: PA_EUNSUPPORTED)."""
+        fn = a.function
+        if a.filter is not None:
+            raise UnsupportedQuery("%s with a FILTER (WHERE ...) clause" % fn)
+        if str(self.query.options.get("enableNullHandling", "false")).lower() == "true":
+            raise UnsupportedQuery("%s with null handling" % fn)
+        for what, c in (("value", a.column), ("time", a.time_column)):
+            if isinstance(c, Q.Expr):
+                raise UnsupportedQuery("%s over a transform expression as its %s column" % (fn, what))
+            for sg in self.segs:
+                col = sg.column(c)
+                if not col.single_value:
+                    raise UnsupportedQuery("%s over the multi-value %s column %s" % (fn, what, c))
+                if col.data_type == "BYTES":
+                    raise UnsupportedQuery("%s over the BYTES %s column %s" % (fn, what, c))
+        tcols = [sg.column(a.time_column) for sg in self.segs]
+        if tcols[0].data_type not in ("INT", "LONG"):
+            raise UnsupportedQuery("%s: the time column %s is %s, not INT or LONG" % (fn, a.time_column, tcols[0].data_type))
+        if len({bool(c.has_dictionary) for c in tcols}) > 1:
+            raise UnsupportedQuery("%s: the time column %s is dictionary-encoded in some segments only" % (fn, a.time_column))
+        stored = self.segs[0].column(a.column).data_type
+        if (a.data_type == "STRING") != (stored == "STRING"):
+            raise UnsupportedQuery("%s: '%s' over the %s column %s" % (fn, a.data_type, stored, a.column))
+        if not hasattr(self, "with_time_stored"):
+            self.with_time_stored = {}  # value column -> stored type (fetch converts it to the declared type)
+        self.with_time_stored[a.column] = stored
+
+    def fetch_time_rows(self, pi, num_groups, columns, stream=None):
+        """The winning rows of FIRSTWITHTIME / LASTWITHTIME accumulator `pi` for the groups the last fetch_arrays
+        returned, in its order (pa_query_fetch_time_rows): (segments int32[n], docs int32[n], {column: values}) with every
+        column's cell decoded through the winning segment's dictionary (a list of Python values; None for a group
+        without a row, whose segment and doc are -1). Synchronises `stream`."""
+        n = int(num_groups)
+        ids = self.gsegs[0].column_ids
+        segs = np.full(max(n, 1), -1, dtype=np.int32)
+        docs = np.full(max(n, 1), -1, dtype=np.int32)
+        cells = np.zeros((max(len(columns), 1), max(n, 1)), dtype=np.int64)
+        if n:
+            cids = (ctypes.c_int32 * max(1, len(columns)))(*[ids[c] for c in columns])
+            ptrs = (ctypes.c_void_p * max(1, len(columns)))(*[cells[c].ctypes.data for c in range(len(columns))])
+            L.check(L.lib().pa_query_fetch_time_rows(self.handle, stream, pi, n, len(columns), cids, segs.ctypes.data,
+                                                     docs.ctypes.data, ptrs), "pa_query_fetch_time_rows")
+        segs, docs = segs[:n], docs[:n]
+        out = {}
+        for c, name in enumerate(columns):
+            vals = [None] * n
+            for si, sg in enumerate(self.segs):
+                rows = np.flatnonzero(segs == si)
+                if not len(rows):
+                    continue
+                col = sg.column(name)
+                cc = cells[c, rows]
+                if col.has_dictionary:
+                    got = np.asarray(col.dictionary)[cc].tolist()
+                elif col.data_type in ("FLOAT", "DOUBLE"):  # (the bits of the value as a double)
+                    got = cc.view(np.float64).tolist()
+                else:
+                    got = cc.tolist()
+                for r, v in zip(rows.tolist(), got):
+                    vals[r] = v
+            out[name] = vals
+        return segs, docs, out
 
     def _group_remap(self, name, table_dict, dictionary):
         """int32[len(dictionary)]: the table-wide key id of every value of a segment's dictionary of group-by column
@@ -697,7 +830,8 @@ class GpuQueryExecutor:
         out["plan"]["strategy"] = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane", 6: "lane", 7: "lane",
                                     8: "lds_dense", 9: "lds_dense", 10: "lds_dense", 11: "lds_dense", 12: "lds_dense",
                                     14: "lds_dense", 15: "lds_dense", 128: "select", 129: "distinct",
-                                    130: "distinct", 131: "filtered", 132: "filtered", 133: "expr", 134: "expr"}[code]
+                                    130: "distinct", 131: "filtered", 132: "filtered", 133: "expr", 134: "expr",
+                                    135: "time_rows", 136: "time_rows"}[code]
         out["plan"]["variant"] = STRATEGY_VARIANTS.get(code, str(code))
         out["plan"]["eager_literals"] = int(L.lib().pa_query_num_eager_literals(self.handle))
         out["plan"]["lane_major"] = int(L.lib().pa_query_lane_major(self.handle))
@@ -708,6 +842,9 @@ class GpuQueryExecutor:
         out["plan"]["partition_keys"] = int(L.lib().pa_query_partition_keys(self.handle))
         out["plan"]["limit_trimming"] = int(L.lib().pa_query_limit_trimming(self.handle))
         out["plan"]["results_invalid"] = int(L.lib().pa_query_results_invalid(self.handle))
+        # FIRSTWITHTIME / LASTWITHTIME accumulators: {accumulator index: 1 = packed, 2 = wide} (pa_query_time_row_form)
+        out["plan"]["time_row_form"] = {i: int(L.lib().pa_query_time_row_form(self.handle, i))
+                                        for i, (t, _, _) in enumerate(self.pa_aggs) if t in TIME_ROW_AGGS}
         return out
 
     def fetch_arrays(self, stream=None, pooled=False, trim_spec=None):
@@ -737,8 +874,9 @@ class GpuQueryExecutor:
                     o = alloc(i, cap << log2m, np.uint8)
                 elif t == L.PA_AGG_DISTINCTCOUNT:
                     o = alloc(i, cap * self._presence_stride(i), np.uint8)
-                elif t == L.PA_AGG_VALUE_HISTOGRAM:
-                    outs.append(None)  # (pa_query_fetch writes nothing: fetch_histograms / percentiles read the bins)
+                elif t == L.PA_AGG_VALUE_HISTOGRAM or t in TIME_ROW_AGGS:
+                    # (pa_query_fetch writes nothing: fetch_histograms / percentiles read the bins, fetch_time_rows the rows)
+                    outs.append(None)
                     continue
                 else:
                     o = alloc(i, cap, np.float64)
@@ -1057,6 +1195,16 @@ class GpuQueryExecutor:
                 key_cols[j] = [T.DoubleKey(v) for v in key_cols[j]]
         cols = []  # one python list per query aggregation
         hists = {}
+        # FIRSTWITHTIME / LASTWITHTIME: one fetch per accumulator, over the union of its value columns + the time column
+        time_rows = {}
+        for a, pi in zip(q.aggregations, self.agg_map):
+            if a.function in Q.WITH_TIME_FUNCTIONS:
+                want = time_rows.setdefault(pi, [a.time_column])
+                if a.column not in want:
+                    want.append(a.column)
+        for pi, want in list(time_rows.items()):
+            segs_, _, vals_ = self.fetch_time_rows(pi, n, want, stream)
+            time_rows[pi] = (segs_, vals_)
         lane_counts = self.fetch_lane_counts(n, stream) if self.dev_filters and not self.match_none else None
         group_counts = counts
         for ai, (a, pi) in enumerate(zip(q.aggregations, self.agg_map)):
@@ -1093,6 +1241,12 @@ class GpuQueryExecutor:
                 if pi not in hists:
                     hists[pi] = self.fetch_histograms(pi, n, stream)
                 cols.append(hists[pi])
+            elif a.function in Q.WITH_TIME_FUNCTIONS:
+                segs_, vals_ = time_rows[pi]
+                stored = self.with_time_stored[a.column]  # (from the plan: a placeholder plan leaves no segment here)
+                cols.append([with_time_default(a.function, a.data_type) if segs_[r] < 0 else
+                             ValueTimePair(java_cast(vals_[a.column][r], stored, a.data_type), int(vals_[a.time_column][r]))
+                             for r in range(n)])
             elif a.function in Q.DISTINCT_SET_FUNCTIONS:
                 # the value set of BaseDistinctAggregateAggregationFunction (DISTINCTCOUNT / DISTINCTSUM / DISTINCTAVG)
                 vd = self.value_dicts[pi]
@@ -1146,7 +1300,9 @@ class GpuQueryExecutor:
 STRATEGY_VARIANTS = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lane_cnt", 6: "lane_raw", 7: "lane_dict",
                      8: "gdense4", 9: "gdense8", 10: "gdense12", 11: "gdense_rs12", 12: "gdense_rs8", 14: "gdense_lm8",
                      15: "gdense_lm16", 128: "select", 129: "distinct_lds", 130: "distinct_global",
-                     131: "filtered_lds", 132: "filtered_global", 133: "expr_lds", 134: "expr_global"}
+                     131: "filtered_lds", 132: "filtered_global", 133: "expr_lds", 134: "expr_global",
+                     135: "time_rows_lds", 136: "time_rows_global"}
+TIME_ROW_AGGS = (L.PA_AGG_LAST_ROW_BY_TIME, L.PA_AGG_FIRST_ROW_BY_TIME)
 
 
 class SelectionExecutor(GpuQueryExecutor):
@@ -1433,6 +1589,8 @@ class DistinctExecutor(GpuQueryExecutor):
 def _empty_value(a):
     """An aggregation function's intermediate result over no docs."""
     fn = Q.base_function(a.function)
+    if fn in Q.WITH_TIME_FUNCTIONS:
+        return with_time_default(fn, a.data_type)
     return ({"COUNT": 0, "SUM": 0.0, "MIN": float("inf"), "MAX": float("-inf")}.get(fn) if fn in
             ("COUNT", "SUM", "MIN", "MAX") else
             AvgPair(0.0, 0) if fn == "AVG" else

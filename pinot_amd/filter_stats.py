@@ -492,6 +492,7 @@ def projected_columns(query):
         Q.item_columns(g, cols)
     for a in query.aggregations:
         Q.item_columns(a.column, cols)
+        Q.item_columns(a.time_column, cols)  # (FIRSTWITHTIME / LASTWITHTIME: 7 x docs, LastWithTimeQueriesTest.java:225)
     return len(cols)
 
 

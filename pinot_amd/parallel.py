@@ -28,6 +28,10 @@ SECTION_OP = {
     L.PA_ACC_HIST_U64: dist.ReduceOp.SUM,  # PERCENTILE value histogram bins (DoubleArrayList.addAll)
     L.PA_ACC_LANE_COUNT_U64: dist.ReduceOp.SUM,  # filtered aggregations: docs of every lane in every group
     L.PA_ACC_KEYS_I64: None,  # not element-wise reducible (hashed key spaces)
+    # FIRSTWITHTIME / LASTWITHTIME: the winning row's segment index is rank-local and its values live on the rank that
+    # holds it: not element-wise reducible (refuse_time_rows raises before any collective)
+    L.PA_ACC_TIME_ROW_U64: None,
+    L.PA_ACC_TIME_MAX_I64: None,
 }
 SECTION_DTYPE = {
     L.PA_ACC_COUNT_U64: torch.int64,
@@ -42,6 +46,8 @@ SECTION_DTYPE = {
     L.PA_ACC_HIST_U64: torch.int64,
     L.PA_ACC_LANE_COUNT_U64: torch.int64,
     L.PA_ACC_KEYS_I64: torch.int64,
+    L.PA_ACC_TIME_ROW_U64: torch.int64,
+    L.PA_ACC_TIME_MAX_I64: torch.int64,
 }
 # identity of each per-key section (what pa_query_reset leaves in an empty slot)
 SECTION_IDENTITY = {
@@ -49,6 +55,20 @@ SECTION_IDENTITY = {
     L.PA_ACC_MAX_I64: -(1 << 63),
     L.PA_ACC_KEYS_I64: (1 << 63) - 1,  # the empty-slot marker
 }
+
+
+TIME_ROWS_REASON = ("FIRSTWITHTIME / LASTWITHTIME across GPUs: the accumulator holds each group's winning (segment, doc), "
+                    "a segment index that is local to its rank, and the row's values live on the rank that owns it, so "
+                    "the sections are not element-wise reducible (multi-GPU merge is not supported: merge the ranks' "
+                    "fetched results with reduce.merge_intermediate)")
+
+
+def refuse_time_rows(query):
+    """Raises UnsupportedQuery for a distributed query with FIRSTWITHTIME / LASTWITHTIME, before any collective."""
+    from .engine import UnsupportedQuery
+    from .query import WITH_TIME_FUNCTIONS
+    if any(a.function in WITH_TIME_FUNCTIONS for a in query.aggregations):
+        raise UnsupportedQuery(TIME_ROWS_REASON)
 
 
 def shard_segments(num_segments, rank, world_size):
@@ -375,6 +395,7 @@ def table_layout(query, segments, group=None):
     (presence byte j must mean the same value on every rank before the uint8-MAX reduce ORs them) and the largest
     rank's hashed key bound (every rank's hashed table then has the same slots). Returns a TableLayout; build every
     rank's executor with GpuQueryExecutor(..., **layout.executor_kwargs())."""
+    refuse_time_rows(query)
     segments = [s for s in segments if s.num_docs > 0]  # (empty segments hold no columns: SegmentColumnarIndexCreator)
     local = {"dicts": {}, "vals": {}, "wide": sorted(wide_sum_columns_local(query, segments)),
              "hb": hash_keys_bound_local(query, segments), "schema": {}}
@@ -499,6 +520,8 @@ class DistributedAccumulators:
 
     def __init__(self, executor, device):
         hashed = getattr(executor, "hashed", False)
+        if getattr(executor, "query", None) is not None:
+            refuse_time_rows(executor.query)  # (before any collective: every rank holds the same query)
         if getattr(executor, "distinct", None) is not None:
             # (before any collective: every rank holds the same kind of executor)
             raise L.PinotAmdError("a distinct query is not reduced element-wise (RCCL has no bitwise-OR reduction and the "

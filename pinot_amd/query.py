@@ -18,7 +18,8 @@ REGEXP_LIKE / LIKE become RegexpLikePredicate as in RequestContextUtils.java:231
 Comparison predicates become RangePredicate exactly as the reference's RequestContextUtils does
 (pinot-common/.../request/context/RequestContextUtils.java: >, >=, <, <=, BETWEEN -> RANGE).
 Aggregations: COUNT(*), SUM, MIN, MAX, AVG, MINMAXRANGE, DISTINCTCOUNT, DISTINCTSUM, DISTINCTAVG, DISTINCTCOUNTHLL(col[, log2m]), DISTINCTCOUNTRAWHLL(col[, log2m]) and their *MV
-forms; PERCENTILE<digits>(col), PERCENTILE<digits>MV(col), PERCENTILE(col, p), PERCENTILEMV(col, p).
+forms; PERCENTILE<digits>(col), PERCENTILE<digits>MV(col), PERCENTILE(col, p), PERCENTILEMV(col, p);
+FIRSTWITHTIME(dataCol, timeCol, 'dataType') and LASTWITHTIME(...) (any case, with or without underscores).
 """
 import decimal
 import re
@@ -172,6 +173,16 @@ PERCENTILE_FUNCTIONS = ("PERCENTILE", "PERCENTILEMV")
 _PERCENTILE_ONE_ARG = re.compile(r"(\d+)(MV)?$")
 
 
+# FirstWithTimeAggregationFunction / LastWithTimeAggregationFunction: the intermediate result is the pair (value, time)
+# of the group's winning doc (engine.ValueTimePair), the final result its value. The declared data types the factory
+# takes (AggregationFunctionFactory.java:224-252, :324-350) and its names in messages
+WITH_TIME_FUNCTIONS = ("FIRSTWITHTIME", "LASTWITHTIME")
+WITH_TIME_TYPES = ("BOOLEAN", "INT", "LONG", "FLOAT", "DOUBLE", "STRING")
+_WITH_TIME_LABEL = {"FIRSTWITHTIME": ("FIRST_WITH_TIME", "firstWithTime"), "LASTWITHTIME": ("LAST_WITH_TIME", "lastWithTime")}
+_DATA_TYPES = ("INT", "LONG", "FLOAT", "DOUBLE", "BIG_DECIMAL", "BOOLEAN", "TIMESTAMP", "STRING", "JSON", "BYTES", "STRUCT",
+               "MAP", "LIST", "UNKNOWN")
+
+
 def java_double_string(x):
     """Double.toString of a finite double: the shortest digits that round-trip (Python's repr gives the same digits),
     plain notation from 1e-3 up to 1e7, computerized scientific notation (1.0E-5) outside."""
@@ -288,6 +299,8 @@ class Aggregation:
     percentile: float = -1.0   # PERCENTILE / PERCENTILEMV: 0..100
     version: int = 0           # PERCENTILE spelling: 0 = PERCENTILE<digits>(col), 1 = PERCENTILE(col, p)
     filter: object = None      # AGG(col) FILTER (WHERE filter): the filter tree, as written (no optimizer rewrite)
+    time_column: object = None  # FIRSTWITHTIME / LASTWITHTIME: the time column's name (or the Expr written there)
+    data_type: str = ""        # FIRSTWITHTIME / LASTWITHTIME: the declared type, upper case (WITH_TIME_TYPES)
 
     @property
     def result_name(self):
@@ -310,6 +323,10 @@ class Aggregation:
             if self.version == 0:
                 return "percentile%d%s(%s)" % (int(self.percentile), mv, self.column)
             return "percentile%s(%s, %s)" % (mv, self.column, java_double_string(self.percentile))
+        if self.function in WITH_TIME_FUNCTIONS:
+            # lastwithtime(intColumn,timestampColumn,'INT') (LastWithTimeQueriesTest.java:239-244): no spaces, the type
+            # literal upper-cased in quotes
+            return "%s(%s,%s,'%s')" % (self.function.lower(), self.column, self.time_column, self.data_type)
         return "%s(%s)" % (self.function.lower(), self.column)
 
 
@@ -359,6 +376,7 @@ class Query:
             item_columns(g, cols)
         for a in self.aggregations:
             item_columns(a.column, cols)
+            item_columns(a.time_column, cols)
             filter_columns(a.filter, cols)
         if self.is_selection or self.is_distinct:
             cols.update(self.select_columns)
@@ -490,6 +508,8 @@ class _Parser:
             return Aggregation("COUNT")
         if fn.startswith("PERCENTILE"):
             return self.percentile(fn)
+        if fn.replace("_", "") in WITH_TIME_FUNCTIONS:
+            return self.with_time(fn.replace("_", ""))
         col = self.item()
         log2m = DEFAULT_HLL_LOG2M
         if self.op(","):
@@ -567,6 +587,38 @@ class _Parser:
         """The next tokens start an aggregation: name( where the name is no transform function."""
         tok, nxt = self.peek(), self.peek(1)
         return tok[0] == "id" and nxt == ("op", "(") and tok[1].replace("_", "").lower() not in TRANSFORM_NAMES
+
+    def with_time(self, fn):
+        """AggregationFunctionFactory.java:224-252 (FIRSTWITHTIME) and :324-350 (LASTWITHTIME): exactly three arguments,
+        the third a literal naming one of WITH_TIME_TYPES in any case; the factory's messages."""
+        label, usage = _WITH_TIME_LABEL[fn]
+        usage = "The function can be used as %s(dataColumn, timeColumn, 'dataType')" % usage
+        args = []
+        if not self.op(")"):
+            while True:
+                args.append(self.expr())
+                if not self.op(","):
+                    break
+            self.expect_op(")")
+        if len(args) != 3:
+            raise ValueError("%s expects 3 arguments, got: %d. %s" % (label, len(args), usage))
+        lit = args[2]
+        if isinstance(lit, Expr) or lit[0] != "lit":
+            raise ValueError("%s expects the 3rd argument to be literal, got: %s. %s"
+                             % (label, "FUNCTION" if isinstance(lit, Expr) else "IDENTIFIER", usage))
+        dtype = str(lit[1]).upper()
+        if dtype not in _DATA_TYPES:  # (DataType.valueOf)
+            raise ValueError("No enum constant org.apache.pinot.spi.data.FieldSpec.DataType.%s" % dtype)
+        if dtype not in WITH_TIME_TYPES:
+            raise ValueError("Unsupported data type for %s: %s" % (label, dtype))
+
+        def operand(e):
+            if isinstance(e, Expr):
+                return e
+            if e[0] != "id":
+                raise ValueError("expected a column or an expression, not the literal %r" % (e[1],))
+            return e[1]
+        return Aggregation(fn, operand(args[0]), time_column=operand(args[1]), data_type=dtype)
 
     def percentile(self, fn):
         """AggregationFunctionFactory.java:66-175 for the exact percentile: PERCENTILE<digits>(col) and
@@ -801,7 +853,7 @@ def query_columns(query):
             names.append(f.column)
     if query.filter is not None:
         walk(query.filter)
-    for n in list(query.group_by) + [a.column for a in query.aggregations if a.column] + \
+    for n in list(query.group_by) + [c for a in query.aggregations for c in (a.column, a.time_column) if c] + \
             (list(query.select_columns) if query.is_distinct else []):
         item_columns(n, names)
     for a in query.aggregations:

@@ -3,7 +3,8 @@
   merge_intermediate   ~ GroupByDataTableReducer / AggregationDataTableReducer merging server DataTables
                          (AggregationFunction.merge: COUNT/SUM +, MIN min, MAX max, AVG pair +, HLL addAll,
                          MINMAXRANGE pair min/max, DISTINCTCOUNT / DISTINCTSUM / DISTINCTAVG set union,
-                         PERCENTILE addAll = value histogram counts added)
+                         PERCENTILE addAll = value histogram counts added,
+                         FIRSTWITHTIME / LASTWITHTIME the pair of the earlier / later time, the first argument on a tie)
   server_trim          ~ IndexedTable.finish on the server (IndexedTable.java:149): with ORDER BY keep the top
                          max(limit*5, minServerGroupTrimSize) groups (GroupByUtils.getTableCapacity); without
                          ORDER BY keep `limit` groups (GroupByCombineOperator.java:63-73)
@@ -39,6 +40,10 @@ def merge_value(fn, a, b):
         return set(a) | set(b)
     if fn == "PERCENTILE":  # PercentileAggregationFunction.merge: DoubleArrayList.addAll (counts add per value)
         return a.merge(b)
+    if fn == "LASTWITHTIME":  # LastWithTimeAggregationFunction.merge (:223): the first argument wins equal times
+        return a if a.time >= b.time else b
+    if fn == "FIRSTWITHTIME":  # FirstWithTimeAggregationFunction.merge (:227)
+        return a if a.time <= b.time else b
     raise ValueError(fn)
 
 
@@ -74,6 +79,12 @@ def final_value(fn, v):
         if fn == "DISTINCTSUM":
             return s
         return s / len(v) if len(v) else math.nan
+    if fn in Q.WITH_TIME_FUNCTIONS:
+        # extractFinalResult: the pair's value; a 'BOOLEAN' pair holds the int (IntLongPair), the BOOLEAN result column
+        # shows value != 0
+        if agg is not None and agg.data_type == "BOOLEAN":
+            return v.value != 0
+        return v.value
     return v
 
 
