@@ -865,6 +865,12 @@ int32_t pa_query_eq_prefilter(const pa_query* q);
  * wave's first tiles, segment crossings, a PA_QF_DEBUG_STREAM_ONLY run) keep the default policy. 0 otherwise, <0 if
  * not prepared. */
 int32_t pa_query_stream_nt(const pa_query* q);
+/* 1 when the scan runs the kernel compiled for this query's shape by hiprtc at prepare (eqs_jit.hip): one equality on a
+ * single-value dictionary column of up to 24 bits as the first clause, every other clause one dictId range read per
+ * surviving doc, COUNT / integer SUM over dictionary columns on global accumulators. By default only behind a
+ * dictionary of at least 4096 values; tuning eq_jit 0 / 1 turns it off / on wherever the shape fits. The plan's
+ * strategy stays that of the generic kernel it restates. 0 otherwise, <0 if not prepared. */
+int32_t pa_query_eq_jit(const pa_query* q);
 /* Keys per partition of the partitioned plan's V stream (a power of two, or under the count-free emit any count that
  * spreads the key space over whole rounds of pass C's workgroups), 0 when the plan is not partitioned, <0 if not
  * prepared. */

@@ -81,7 +81,7 @@ EXPORTED = [
     "pa_query_set_expressions",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
-    "pa_query_partition_keys",
+    "pa_query_eq_jit", "pa_query_partition_keys",
     "pa_query_accumulator_bytes", "pa_query_set_accumulator_buffer", "pa_query_num_sections", "pa_query_section",
     "pa_query_fetch", "pa_query_fetch_trimmed", "pa_query_fetch_histogram", "pa_query_percentiles",
     "pa_query_fetch_time_rows", "pa_query_time_row_form", "pa_query_matched_docs", "pa_query_key_layout", "pa_query_limit_trimming",
@@ -244,6 +244,7 @@ def _declare(lib):
         "pa_query_count_free_emit": (i32, [vp]),
         "pa_query_eq_prefilter": (i32, [vp]),
         "pa_query_stream_nt": (i32, [vp]),
+        "pa_query_eq_jit": (i32, [vp]),
         "pa_query_partition_keys": (i32, [vp]),
         "pa_query_accumulator_bytes": (u64, [vp]),
         "pa_query_set_accumulator_buffer": (ctypes.c_int, [vp, vp, u64]),

@@ -26,7 +26,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomic
          "-Wall", "-Wno-unused-function"]
 # kernels compiled at query prepare by hiprtc (pa_jit.hip): their sources become string literals (*_src.inc), with the
 # descriptor header they share with the host pasted in
-JIT_SOURCES = ["gdl_jit.hip", "pve_jit.hip"]
+JIT_SOURCES = ["gdl_jit.hip", "pve_jit.hip", "eqs_jit.hip"]
 JIT_ABI = "pa_jit_abi.h"
 _INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 

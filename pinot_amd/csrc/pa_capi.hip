@@ -321,6 +321,7 @@ int pa_query_prepare(pa_query* q) {
     PA_HIP(hipMemcpy(q->dq_pass2.p, &h2, sizeof(DevQuery), hipMemcpyHostToDevice));
   }
   if (!q->is_distinct) rc = jit_plan(q, P, cus);
+  if (!rc) rc = eqs_plan(q, P, cus);
   if (rc) return rc;
   if (q->is_distinct) {
     rc = distinct_plan(q);
@@ -469,12 +470,13 @@ int pa_query_scan(pa_query* q, void* stream) {
     a->used = true;
     return PA_OK;
   }
-  if (q->jit_fn) {  // the query-shape specialised dense kernel
+  if (q->jit_fn) {  // the query-shape specialised kernel: dense GROUP BY, or the direct scan of one equality
     void* pa = q->jit_args.p;
     void* ps = q->jit_segs.p;
     void* params[] = {&pa, &ps};
     PA_HIP(hipModuleLaunchKernel(q->jit_fn, q->jit_grid, 1, 1, q->jit_waves * kWave, 1, 1, q->jit_lds, st, params,
                                  nullptr));
+    if (q->eq_jit) q->leap_searched = false;  // (as after the generic scan below)
     return PA_OK;
   }
   PartScratch none{};
@@ -589,7 +591,7 @@ int pa_query_plan(const pa_query* q, int32_t* strategy, int32_t* steps, int32_t*
   if (!q || !q->prepared) return fail(PA_EINVAL, "query not prepared");
   // (the query-shape specialised kernel reports the lane-major dense variant it specialises)
   if (strategy)
-    *strategy = q->jit_fn ? (q->jit_waves >= 16 ? STRAT_GDENSE_LM16 : STRAT_GDENSE_LM8)
+    *strategy = q->jit_fn && !q->eq_jit ? (q->jit_waves >= 16 ? STRAT_GDENSE_LM16 : STRAT_GDENSE_LM8)
                           : (q->partitioned ? STRAT_PEMIT : q->strategy);
   if (steps) *steps = q->steps;
   if (dma_slots) *dma_slots = q->dma_slots;
@@ -610,6 +612,7 @@ int32_t pa_query_time_row_form(const pa_query* q, int32_t agg) {
 int32_t pa_query_lane_major(const pa_query* q) { return q && q->prepared ? q->lane_major : -1; }
 int32_t pa_query_eq_prefilter(const pa_query* q) { return q && q->prepared ? q->eq_prefilter : -1; }
 int32_t pa_query_stream_nt(const pa_query* q) { return q && q->prepared ? q->stream_nt : -1; }
+int32_t pa_query_eq_jit(const pa_query* q) { return q && q->prepared ? q->eq_jit : -1; }
 int32_t pa_query_count_free_emit(const pa_query* q) { return q && q->prepared ? (q->pve.fn ? (q->pvh.fn ? 2 : 1) : 0) : -1; }
 int32_t pa_query_partition_keys(const pa_query* q) {
   if (!q || !q->prepared) return -1;
@@ -617,7 +620,7 @@ int32_t pa_query_partition_keys(const pa_query* q) {
   return q->hq.part_kr_v ? q->hq.part_kr_v : (int32_t)1 << q->hq.kshift_v;
 }
 int32_t pa_query_dense_packed(const pa_query* q) {
-  return q && q->prepared ? (q->jit_fn ? 2 : (q->dense_packed ? 1 : 0)) : -1;
+  return q && q->prepared ? (q->jit_fn && !q->eq_jit ? 2 : (q->dense_packed ? 1 : 0)) : -1;
 }
 
 int32_t pa_query_column_staged(const pa_query* q, int32_t column_id) {

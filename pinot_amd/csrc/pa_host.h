@@ -254,6 +254,7 @@ struct pa_query {
   hipFunction_t jit_fn = nullptr;
   int jit_waves = 0, jit_grid = 0, jit_lds = 0, jit_nd = 16, jit_nseg = 0, jit_classes = 0, jit_slots = 0;
   std::vector<int> jit_cols;  // the column slots the specialised kernel stages (pa_query_column_staged)
+  int eq_jit = 0;  // jit_fn is eqs_jit.hip (one equality, rare survivors: the direct scan's shape), not gdl_jit.hip
   DevBuf jit_args, jit_segs;
   // the partitioned path's V emit without a count pass (pve_jit.hip + pa_pve.hip): null = count + emit passes
   // one per record stream: pve (V), pvh (H records of a DISTINCTCOUNTHLLMV next to a V stream)
@@ -524,6 +525,7 @@ int distinct_plan(pa_query* q);                 // prepare, last: the finish buf
 // pa_jit.hip
 int jit_plan(pa_query* q, const Prep& P, int cus);
 void jit_fill_pointers(pa_query* q, JitArgs& a);
+int eqs_plan(pa_query* q, const Prep& P, int cus);
 void pve_fill_pointers(const pa_query::PveStream& st, unsigned long long* matched, PveArgs& a);
 int pve_plan(pa_query* q, const Prep& P, int cus);
 

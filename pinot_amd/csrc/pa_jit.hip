@@ -1,6 +1,8 @@
 // Query-shape specialised kernels compiled by hiprtc at pa_query_prepare: gdl_jit.hip (dense GROUP BY with packed
-// accumulation) and pve_jit.hip (count-free partitioned emit).
+// accumulation), eqs_jit.hip (the direct scan of one equality with rare survivors) and pve_jit.hip (count-free
+// partitioned emit).
 #include "pa_host.h"
+#include "pa_eq_any.h"
 
 // ---------------------------------------------------------------- query-shape specialisation (gdl_jit.hip)
 // The lane-major dense kernel with packed accumulation, compiled per query shape by hiprtc: every column width, image
@@ -106,6 +108,7 @@ struct JitSum {
 // leaves; every staged column 1..31 bits. Leaves q->jit_fn null (the generic plan runs) otherwise.
 int jit_plan(pa_query* q, const Prep& P, int cus) {
   q->jit_fn = nullptr;
+  q->eq_jit = 0;
   q->jit_cols.clear();
   const pa_query_spec& s = q->spec;
   if (q->nseg == 0 || s.num_group_by != 1 || !P.gd_box_ok || P.gd_box || q->hq.leap_mode || q->partitioned ||
@@ -605,6 +608,164 @@ int jit_plan(pa_query* q, const Prep& P, int cus) {
            "ktab %d kib %d lds %zu drain %d",
            W, ND, RS, RR, ring_n, lmax, (int)segdrain, classes.size(), nslot, slot_b, ni, q->nseg, (int)ktab, (int)kib,
            lds, drain);
+  return PA_OK;
+}
+
+// ---------------------------------------------------------------- one equality, rare survivors (eqs_jit.hip)
+// scan_kernel<STRAT_GLOBAL, 32, 1> restated for the shape of its hoisted single-range loop and compiled per shape: the
+// first clause is one equality on a single-value dictionary column of up to kEqPrefilterMaxNb bits (a DICT_RANGE of
+// span 1, not negated), every other clause one DICT_RANGE, group-by columns and SUM sources single-value dictionary
+// columns, COUNT and integer SUMs only, a direct key space, none of the other query forms. The kernel stages the
+// equality's column alone and reads everything else per surviving doc, whichever clauses the generic plan would have
+// run on staged tiles. It keeps the generic launch's tile space, grid, waves, ring depth and fused-statistics buffers,
+// so everything after the scan reads what it always read. Tuning eq_jit: 0 never, 1 whenever the shape fits, auto only
+// behind a dictionary of at least 4096 values (fewer: survivors are not rare, and the generic kernel's batched
+// survivor code is the better one). Leaves q->jit_fn null (the generic kernel runs) otherwise, or when hiprtc fails.
+static const char* kEqsJitSrc =
+#include "eqs_jit_src.inc"
+    ;
+constexpr int kEqJitMinCard = 4096;
+
+int eqs_plan(pa_query* q, const Prep& P, int cus) {
+  (void)cus;
+  q->eq_jit = 0;
+  if (q->jit_fn) return PA_OK;
+  const pa_query_spec& s = q->spec;
+  const Tuning& tn = q->tune;
+  const DevQuery& h = q->hq;
+  if (tn.eq_jit == 0 || (s.flags & (PA_QF_NO_JIT | PA_QF_DEBUG_STREAM_ONLY)) || tn.debug_emit) return PA_OK;
+  if (q->nseg == 0 || q->num_tiles == 0 || q->num_tiles >= (uint64_t(1) << 31) || q->strategy != STRAT_GLOBAL || !q->lane_major || q->steps != 32 ||
+      q->hashed || q->partitioned || q->limit_mode || q->limit_walk || q->has_mv || h.gb_mv >= 0 || q->is_select ||
+      q->is_distinct || q->is_filtered || q->is_expr || q->is_trow)
+    return PA_OK;
+  const int nl = (int)q->literals.size(), ng = s.num_group_by;
+  if (nl < 1 || nl - 1 > kJitMax || q->num_eager < 1 || ng > kJitMaxGb || h.num_gb != ng) return PA_OK;
+  for (int li = 0; li < nl; ++li)
+    if (!q->clause_end[li] || s.leaves[q->literals[li].leaf].kind != PA_LEAF_DICT_RANGE) return PA_OK;
+  std::vector<int> sums;
+  for (int a = 0; a < s.num_aggs; ++a) {
+    if (s.aggs[a].type == PA_AGG_COUNT) continue;
+    if (s.aggs[a].type != PA_AGG_SUM || (h.aggs[a].src != SRC_INT && h.aggs[a].src != SRC_LONG)) return PA_OK;
+    sums.push_back(a);
+  }
+  const int na = (int)sums.size();
+  if (na > kJitMax) return PA_OK;
+  auto dict_col = [](const DevCol& c) { return c.kind == COL_SV_DICT && c.words && c.nbits >= 1 && c.nbits <= 32; };
+  const int slot0 = P.leaf_slot[q->literals[0].leaf];
+  std::vector<int> classes, seg_cls(q->nseg, 0);
+  int min_card = INT32_MAX, nb_max = 0;
+  for (int si = 0; si < q->nseg; ++si) {
+    const DevSeg& d = q->hsegs[si];
+    const DevLeaf& L = d.leaves[0];
+    const DevCol& c0 = d.cols[slot0];
+    const int nb = c0.nbits;
+    if (d.admit || !dict_col(c0) || nb > kEqPrefilterMaxNb || L.kind != PA_LEAF_DICT_RANGE || L.negate ||
+        L.nbits != nb || (uint32_t)L.span != (uint32_t)((uint64_t(1) << (32 - nb)) - 1))
+      return PA_OK;
+    for (int li = 1; li < nl; ++li)
+      if (d.leaves[li].kind != PA_LEAF_DICT_RANGE || !dict_col(d.cols[P.leaf_slot[q->literals[li].leaf]])) return PA_OK;
+    for (int j = 0; j < ng; ++j)
+      if (!dict_col(d.cols[h.gb_slot[j]])) return PA_OK;
+    for (int a : sums)
+      if (!dict_col(d.cols[h.aggs[a].slot]) || !d.cols[h.aggs[a].slot].dict_i64) return PA_OK;
+    min_card = std::min(min_card, (int)c0.card);
+    nb_max = std::max(nb_max, nb);
+    auto it = std::find(classes.begin(), classes.end(), nb);
+    if (it == classes.end()) {
+      if (classes.size() == 4) return PA_OK;
+      classes.push_back(nb);
+      it = classes.end() - 1;
+    }
+    seg_cls[si] = (int)(it - classes.begin());
+  }
+  if (tn.eq_jit < 0 && min_card < kEqJitMinCard) return PA_OK;
+  // the generic launch's geometry: waves, grid, ring depth; a tile image holds the one column behind a 16-byte guard
+  const int W = scan_waves(STRAT_GLOBAL), R = h.ring;
+  int dmax = 0;
+  for (int nb : classes) dmax = std::max(dmax, (16 * nb + 63) / 64);
+  if (R < 2 || R > 8 || (R - 2) * dmax >= 64) return PA_OK;
+  const size_t img = al16((size_t)16 + (size_t)256 * nb_max + 16);
+  const size_t lds = (size_t)W * R * img + (h.leap_mode ? (size_t)W * h.leap_lds_cap * 8 : 0);
+  const int wg = std::max(1, std::min(4, q->plan_wg));
+  if (lds * (size_t)wg > kLdsBudget) return PA_OK;
+  std::vector<std::string> defs = {
+      "-DJIT_W=" + std::to_string(W), "-DJIT_WG=" + std::to_string(wg), "-DJIT_RING=" + std::to_string(R),
+      "-DJIT_IMG=" + std::to_string(img / 4), "-DJIT_NCLS=" + std::to_string(classes.size()),
+      "-DJIT_NB=" + int_list(classes), "-DJIT_NT=" + std::to_string(q->stream_nt ? 1 : 0),
+      "-DJIT_NLZ=" + std::to_string(nl - 1), "-DJIT_NG=" + std::to_string(ng), "-DJIT_NA=" + std::to_string(na),
+      "-DJIT_LEAP=" + std::to_string(h.leap_mode ? 1 : 0)};
+  if (tn.eqs_dbg) defs.push_back("-DJIT_DBG=" + std::to_string(tn.eqs_dbg));
+  hipFunction_t fn = jit_compile(defs, kEqsJitSrc, "eqs_jit");
+  if (!fn) return PA_OK;
+  (void)hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  JitArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.total_tiles = h.total_wtiles;
+  a.nseg = q->nseg;
+  a.xcd_major = h.xcd_major;
+  jit_fill_pointers(q, a);
+  std::vector<char> buf(sizeof(EqsHdr) + sizeof(EqsSeg) * (size_t)q->nseg, 0);
+  EqsHdr& hd = *(EqsHdr*)buf.data();
+  EqsSeg* js = (EqsSeg*)(buf.data() + sizeof(EqsHdr));
+  hd.leap_out = h.leap_out;
+  hd.leap_cap = h.leap_cap;
+  hd.leap_slices = h.leap_slices;
+  hd.leap_lds_cap = h.leap_mode ? h.leap_lds_cap : 0;
+  hd.nseg = q->nseg;
+  for (int j = 0; j < ng; ++j) hd.gb_stride[j] = h.gb_stride[j];
+  for (int si = 0; si < q->nseg; ++si) {
+    const DevSeg& d = q->hsegs[si];
+    EqsSeg& j = js[si];
+    const DevLeaf& L = d.leaves[0];
+    const int nb = d.cols[slot0].nbits;
+    j.src = (unsigned long long)(uintptr_t)d.cols[slot0].words;
+    j.first_tile = d.first_wtile;
+    j.num_docs = d.num_docs;
+    j.num_tiles = d.num_wtiles;
+    j.lo_t = (uint32_t)L.lo;
+    j.hi_t = (uint32_t)L.span;
+    j.win = eq_pattern_window(nb, (uint32_t)L.lo >> (32 - nb));
+    j.cls = seg_cls[si];
+    j.index = d.index;
+    for (int li = 1; li < nl; ++li) {  // plain bounds, as pa_scan.h leaf_match_doc takes them from the MSB-aligned pair
+      const DevLeaf& Z = d.leaves[li];
+      const DevCol& c = d.cols[P.leaf_slot[q->literals[li].leaf]];
+      const int sh = 32 - c.nbits;
+      EqsLeaf& z = j.lazy[li - 1];
+      z.words = (unsigned long long)(uintptr_t)c.words;
+      z.lo = (uint32_t)Z.lo >> sh;
+      z.span = (uint32_t)(((uint64_t)(uint32_t)Z.span + 1u) >> sh);
+      z.nb = c.nbits;
+      z.neg = Z.negate ? 1 : 0;
+    }
+    for (int g = 0; g < ng; ++g) {
+      const DevCol& c = d.cols[h.gb_slot[g]];
+      j.gb[g].words = (unsigned long long)(uintptr_t)c.words;
+      j.gb[g].tab = (unsigned long long)(uintptr_t)d.remap[g];
+      j.gb[g].nb = c.nbits;
+    }
+    for (int k = 0; k < na; ++k) {
+      const DevCol& c = d.cols[h.aggs[sums[k]].slot];
+      j.sum[k].words = (unsigned long long)(uintptr_t)c.words;
+      j.sum[k].tab = (unsigned long long)(uintptr_t)c.dict_i64;
+      j.sum[k].nb = c.nbits;
+    }
+  }
+  int rc = dev_alloc(q->jit_args, sizeof(JitArgs));
+  if (!rc) rc = dev_alloc(q->jit_segs, buf.size());
+  if (rc) return rc;
+  PA_HIP(hipMemcpy(q->jit_args.p, &a, sizeof(a), hipMemcpyHostToDevice));
+  PA_HIP(hipMemcpy(q->jit_segs.p, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  q->jit_fn = fn;
+  q->eq_jit = 1;
+  q->jit_waves = W;
+  q->jit_lds = (int)lds;
+  q->jit_grid = q->grid;
+  q->jit_nseg = q->nseg;
+  q->jit_classes = (int)classes.size();
+  q->jit_cols.assign(1, slot0);
+  PLAN_LOG("eqs_jit: W %d grid %d ring %d classes %zu nt %d lazy %d gb %d sums %d leap %d lds %zu", W, q->grid, R,
+           classes.size(), q->stream_nt, nl - 1, ng, na, h.leap_mode, lds);
   return PA_OK;
 }
 

@@ -1,4 +1,5 @@
-// Descriptors the host (pa_jit.hip) writes and the hiprtc-compiled query-shape kernels (gdl_jit.hip, pve_jit.hip) read.
+// Descriptors the host (pa_jit.hip) writes and the hiprtc-compiled query-shape kernels (gdl_jit.hip, eqs_jit.hip,
+// pve_jit.hip) read.
 // One definition for both sides: pa_jit.hip includes this file, and build.py pastes it into the kernels' source
 // strings in place of their #include line (hiprtc sees no include path), so the layouts cannot drift apart. Plain
 // built-in types only (the hiprtc side has no <cstdint>).
@@ -41,6 +42,41 @@ struct JitArgs {
 };
 static_assert(sizeof(JitSeg) == 48 + 8 + 8 + 48 + 16 + 24 + 8 + 48 + 48 + 24 + 24 + 8, "JitSeg layout");
 static_assert(sizeof(JitArgs) == 8 + 24 + 8 + 8 + 8 + 48 + 24 + 48 + 48, "JitArgs layout");
+
+// ---------------------------------------------------------------- eqs_jit.hip (one equality, rare survivors)
+// The kernel's arguments are a JitArgs (total_tiles, nseg, xcd_major and the accumulator pointers: matched, count, sum,
+// sum_long; the rest unused) and an EqsHdr with the bound segments' EqsSeg right behind it. A segment's values are
+// read with scalar loads at a segment switch, the lazy clauses' and the post-filter columns' only for surviving docs.
+struct EqsLeaf {                        // one lazy DICT_RANGE clause: (dictId - lo) < span, then the negation
+  unsigned long long words;             // the column's stream, past the guard words
+  unsigned int lo, span;
+  int nb, neg;
+};
+struct EqsCol {                         // a group-by column or a SUM's column
+  unsigned long long words;
+  unsigned long long tab;               // group-by: dictId -> table key id (int32), 0 = identity; SUM: the int64 dictionary
+  int nb, pad;
+};
+struct EqsSeg {
+  unsigned long long src;               // the equality column's stream, past the guard words
+  long long first_tile;                 // first 2048-doc tile in the query's tile space
+  int num_docs, num_tiles;
+  unsigned int lo_t, hi_t;              // the equality as an MSB-aligned range (pa_scan.h leaf_lm)
+  unsigned long long win;               // its dictId repeated every nb bits (pa_eq_any.h eq_pattern_window)
+  int cls, index;                       // width class (JIT_NB[cls]); position in the query's segment list
+  EqsLeaf lazy[kJitMax];
+  EqsCol gb[kJitMaxGb];
+  EqsCol sum[kJitMax];
+};
+struct EqsHdr {
+  unsigned long long* leap_out;         // fused execution statistics (pa_scan.h): counters, wave counts, list slices
+  long long leap_cap, leap_slices;
+  int leap_lds_cap, nseg;
+  long long gb_stride[kJitMaxGb];       // table-wide key = sum_j key id_j * gb_stride[j]
+};
+static_assert(sizeof(EqsLeaf) == 24 && sizeof(EqsCol) == 24, "EqsLeaf / EqsCol layout");
+static_assert(sizeof(EqsSeg) == 48 + 24 * (kJitMax + kJitMaxGb + kJitMax), "EqsSeg layout");
+static_assert(sizeof(EqsHdr) == 32 + 8 * kJitMaxGb, "EqsHdr layout");
 
 // ---------------------------------------------------------------- pve_jit.hip (count-free partitioned emit)
 struct PveSeg {

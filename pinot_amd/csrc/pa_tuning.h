@@ -57,6 +57,11 @@
      only when one launch stages more bytes than L2 + Infinity Cache hold, so a smaller table that is queried again    \
      keeps its cache hits) */                                                                                          \
   X(stream_nt, -1, 0, 1, 0)                                                                                            \
+  /* eqs_jit.hip (eqs_plan): the direct scan of one equality compiled per query shape, 0 never / 1 wherever the shape \
+     fits (default: only behind a dictionary of at least 4096 values, where surviving docs are rare) */               \
+  X(eq_jit, -1, 0, 1, 0)                                                                                               \
+  /* eqs_jit.hip JIT_DBG: 1 = stream the tiles only, through the same (nt) DMAs and counted waits */                  \
+  X(eqs_dbg, 0, 0, 1, 1)                                                                                               \
   /* workgroups of the non-partitioned scan launch (default: one wave per tile up to the resident workgroups). A      \
      small grid gives every wave several tiles of a small table, so tests reach the hoisted steady-state loops */      \
   X(scan_grid, -1, 1, 4096, 0)                                                                                         \

@@ -839,6 +839,7 @@ class GpuQueryExecutor:
         out["plan"]["count_free_emit"] = int(L.lib().pa_query_count_free_emit(self.handle))
         out["plan"]["eq_prefilter"] = int(L.lib().pa_query_eq_prefilter(self.handle))
         out["plan"]["stream_nt"] = int(L.lib().pa_query_stream_nt(self.handle))
+        out["plan"]["eq_jit"] = int(L.lib().pa_query_eq_jit(self.handle))
         out["plan"]["partition_keys"] = int(L.lib().pa_query_partition_keys(self.handle))
         out["plan"]["limit_trimming"] = int(L.lib().pa_query_limit_trimming(self.handle))
         out["plan"]["results_invalid"] = int(L.lib().pa_query_results_invalid(self.handle))
