@@ -52,6 +52,13 @@
  *      time >= / <= the best so far takes over, :112,147,196 / :111,147,200) and the in-server merge (:223 / :227) become
  *      one 64-bit max per group inside the scan; extractAggregationResult / extractGroupByResult (the ValueTimePair)
  *      the winning (segment, doc) and the cells a finish kernel reads there.
+ *  pa_query_set_moments / pa_query_fetch_moments / pa_query_moments_form (PA_AGG_MOMENTS)
+ *      replace aggregation/function/VarianceAggregationFunction.java (VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP) and
+ *      CovarianceAggregationFunction.java (COVAR_POP / COVAR_SAMP; factory cases AggregationFunctionFactory.java:413-427):
+ *      aggregate / aggregateGroupBySV (VarianceTuple.apply per doc; the raw sums of CovarianceAggregationFunction.java:100-108)
+ *      and the in-server merge become moment sums kept per group inside the scan — exact integers for int32-range
+ *      INT / LONG columns, pivoted power sums in double otherwise; extractAggregationResult / extractGroupByResult the
+ *      VarianceTuple (count, sum, m2) / CovarianceTuple (sumX, sumY, sumXY, count) columns a finish kernel writes.
  *  pa_query_set_selection / pa_query_bind_order_remap / pa_query_fetch_selection
  *      replace, for one segment set on one GPU, operator/query/SelectionOnlyOperator.java,
  *      operator/query/SelectionOrderByOperator.java:108-112 (the comparator), :139-188 (every ordered expression
@@ -174,6 +181,23 @@ extern "C" {
                                       over, FirstWithTimeAggregationFunction.java:111,147,200: among equal winning times
                                       again the greatest (segment bind index, docId) wins); the time key is complemented
                                       inside its width */
+#define PA_AGG_MOMENTS 10 /* VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP of column `column_id`, or — with a second
+                             column named through pa_query_set_moments — COVAR_POP / COVAR_SAMP of the pair: per group
+                             the moment sums all of these finish from, so the spellings over one column (pair) share one
+                             aggregation. Integer form (every argument column INT / LONG with all values inside int32 in
+                             every bound segment): exact integers — sum x in one int64, sum x^2 (covariance: sum x, sum y,
+                             sum x y) with the product as the 96-bit pair of PA_ACC_SUM_I64X2 — so the result does not
+                             depend on the order of the atomics. Double form (everything else): variance keeps sum d and
+                             sum d^2 of d = x - pivot in double, pivot = the midpoint of the column's minimum and maximum
+                             over the bound segments (0 where that is not finite); covariance keeps the reference's raw
+                             sums of x, y and x y in double. Without pa_query_set_moments every PA_AGG_MOMENTS is a
+                             variance and the library chooses form and pivot (pa_query_moments_form reports them).
+                             pa_query_prepare fails with PA_EUNSUPPORTED over a hashed key space (so over raw group-by
+                             columns and expression keys), for a multi-value group-by or aggregation column in the query,
+                             for an argument column that is multi-value, STRING or BYTES, next to aggregation filters or
+                             expressions, and where numGroupsLimit trimming would run in its first-position + sort form
+                             (the prefix walk admits these updates like any other). pa_query_fetch writes nothing for it:
+                             pa_query_fetch_moments reads the tuples */
 /* SUM / MIN / MAX / DISTINCTCOUNTHLL over a multi-value column aggregate every value of the doc (SUMMV, MINMV, MAXMV,
  * DISTINCTCOUNTHLLMV); a multi-value group-by column expands a doc into one key per value (cartesian product over
  * several MV columns), as DictionaryBasedGroupKeyGenerator.getIntRawKeys does. */
@@ -458,6 +482,28 @@ typedef struct {
  * filter no aggregation uses; PA_EUNSUPPORTED: a filter expanding to more than PA_MAX_LEAVES CNF literals. */
 int pa_query_set_agg_filters(pa_query* q, const pa_agg_filter_spec* spec);
 
+/* ---------------------------------------------------------------- moments (PA_AGG_MOMENTS)
+ * What pa_agg_spec has no room for, per spec.aggs[i] (entries of other aggregation types are ignored). */
+#define PA_MOMENTS_FORM_AUTO 0    /* the library chooses: integer where every argument column allows it */
+#define PA_MOMENTS_FORM_INTEGER 1 /* exact integer sums (PA_ACC_MOM_I64); PA_EINVAL at prepare where a column does not
+                                     fit */
+#define PA_MOMENTS_FORM_DOUBLE 2  /* double sums (PA_ACC_MOM_F64) */
+typedef struct {
+  int32_t second_column[PA_MAX_AGGS]; /* -1: variance of column_id; else covariance of (column_id, second_column) */
+  int32_t form[PA_MAX_AGGS];          /* PA_MOMENTS_FORM_* (ranks of a multi-GPU query pass the agreed form) */
+  int32_t has_pivot[PA_MAX_AGGS];     /* 1: `pivot` is the variance's pivot in the double form (ranks pass the agreed
+                                         value); 0: the library takes the midpoint of the bound segments' min and max */
+  double pivot[PA_MAX_AGGS];          /* must be finite */
+} pa_moments_spec;
+
+/* Between pa_query_create and pa_query_prepare. PA_EINVAL: a form outside PA_MOMENTS_FORM_*, a pivot that is not finite,
+ * a pivot on a covariance. */
+int pa_query_set_moments(pa_query* q, const pa_moments_spec* spec);
+
+/* The form (PA_MOMENTS_FORM_INTEGER / _DOUBLE) and pivot the prepared query uses for aggregation `agg` (either pointer
+ * may be NULL; the pivot of the integer form and of a covariance is 0). PA_EINVAL: not prepared, or not a PA_AGG_MOMENTS. */
+int pa_query_moments_form(const pa_query* q, int32_t agg, int32_t* out_form, double* out_pivot);
+
 /* Docs of every lane in the groups the last pa_query_fetch returned, in the same order (num_groups = that call's
  * result): out[j * num_groups + g] (int64[num_filters * num_groups]) = docs of group g matching W AND F_j. The host
  * reads COUNT and AVG of a filtered aggregation from it. Synchronises `stream`. */
@@ -609,6 +655,15 @@ int pa_query_scan(pa_query* q, void* stream);
                                   live on the rank that holds it */
 #define PA_ACC_TIME_MAX_I64 14 /* the wide form's first word: [key] = the greatest time of the group's docs (FIRST: of
                                   the complemented times), reset identity INT64_MIN; read by the second scan launch */
+/* PA_AGG_MOMENTS: PA_MOMENTS_WORDS = 4 64-bit words per key, [key * 4 + w], reset identity 0, reduce SUM (ranks must agree
+ * on form and pivot). p = x * x for a variance, x * y for a covariance (the second column's value y):
+ *   PA_ACC_MOM_I64  w0 = sum x (int64), w1 = sum y (covariance; else unused), w2 = sum of the low 32 bits of p
+ *                   (unsigned), w3 = sum of p >> 32 (signed): sum p = w3 * 2^32 + w2, as PA_ACC_SUM_I64X2
+ *   PA_ACC_MOM_F64  doubles: w0 = sum x' , w1 = sum y (covariance; else unused), w2 = sum x' * y', w3 unused; variance:
+ *                   x' = y' = x - pivot, covariance: x' = x, y' = y */
+#define PA_ACC_MOM_I64 15
+#define PA_ACC_MOM_F64 16
+#define PA_MOMENTS_WORDS 4
 /* All sections live in one device block of pa_query_accumulator_bytes() bytes (256-byte aligned sections).
  * pa_query_set_accumulator_buffer lets the caller own that block (e.g. memory its collective library
  * registered) instead of the library: call after pa_query_prepare; `bytes` must be >= the size. */
@@ -623,7 +678,7 @@ void* pa_query_section(const pa_query* q, int32_t section, int32_t* kind, int64_
  * COUNT/SUM/MIN/MAX (the reference's intermediate type), uint8[capacity << log2m] for HLL registers. Nothing is
  * written for a VALUE_HISTOGRAM aggregation (0 bytes per group: its out_aggs[i] may be NULL); its bins are read with
  * pa_query_fetch_histogram / pa_query_percentiles. Nor for a LAST / FIRST_ROW_BY_TIME aggregation (0 bytes per group):
- * pa_query_fetch_time_rows reads its rows.
+ * pa_query_fetch_time_rows reads its rows; nor for a PA_AGG_MOMENTS aggregation: pa_query_fetch_moments reads its tuples.
  * For aggregation-only queries key 0 is always returned (count may be 0).
  * Returns the number of groups (may exceed capacity: then only `capacity` were written), <0 on error.
  * capacity = 0 (output pointers may be NULL) only counts the groups — for large key spaces just the GPU count pass —
@@ -644,7 +699,7 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
  * key ids, group-by column 0 most significant, ascending. num_terms = 0 keeps the `trim` smallest key tuples. NaN term
  * values are out of scope: the comparator of the reference is no total order over them.
  * PA_EUNSUPPORTED (the caller trims the full fetch on the host instead): a hashed key space (so any expression key), a
- * query with a VALUE_HISTOGRAM or LAST / FIRST_ROW_BY_TIME aggregation or aggregation filters (their fetch calls follow
+ * query with a VALUE_HISTOGRAM, LAST / FIRST_ROW_BY_TIME or MOMENTS aggregation or aggregation filters (their fetch calls follow
  * the full fetch's group order), more than PA_MAX_TRIM_TERMS terms, a term over any other aggregation type (HLL, DISTINCTCOUNT, COUNT_MV).
  * HLL / DISTINCTCOUNT aggregations that are only read are gathered for the kept groups.
  * Returns min(n, trim) (may exceed capacity: then nothing was written; call again with that capacity), <0 on error;
@@ -707,6 +762,19 @@ int pa_query_fetch_time_rows(pa_query* q, void* stream, int32_t agg, int64_t num
  * everything else the query computes accumulates in the first only), 0 = not such an aggregation, <0 = not prepared or
  * no such aggregation index. Tuning time_rows_wide forces the wide form for raw time columns (pa_tuning.h). */
 int32_t pa_query_time_row_form(const pa_query* q, int32_t agg);
+
+/* The reference's intermediate tuples of PA_AGG_MOMENTS aggregation `agg` for the groups pa_query_fetch returns for the
+ * current accumulators, in the same order (num_groups = that call's result), as columns: out_count int64[num_groups],
+ * out_values[c] double[num_groups] for c < 3 (each pointer may be NULL).
+ *   variance    (VarianceTuple.java)    count, out_values = { sum, m2, unused }
+ *   covariance  (CovarianceTuple.java)  count, out_values = { sumX, sumY, sumXY }
+ * Integer form: the sums are the correctly rounded doubles of the exact integers, and m2 = (n * sum x^2 - (sum x)^2) / n
+ * with the numerator exact in 128 bits, rounded once to double, then divided. Double form: sum = S1 + n * pivot,
+ * m2 = max(0, S2 - S1 * S1 / n) evaluated with fma; covariance sums as accumulated. A group without docs (the
+ * aggregation-only key 0 when no doc matched) gives zeros. One thread per group, one copy per column. Synchronises
+ * `stream`. */
+int pa_query_fetch_moments(pa_query* q, void* stream, int32_t agg, int64_t num_groups, int64_t* out_count,
+                           double* const* out_values);
 
 /* numDocsScanned captured by the last pa_query_fetch (docs that passed the filter; with a multi-value group-by this
  * differs from the sum of the group counts), <0 on error. */

@@ -27,7 +27,7 @@ PA_INT, PA_LONG, PA_FLOAT, PA_DOUBLE, PA_STRING, PA_BYTES = range(6)
 PA_LEAF_DICT_RANGE, PA_LEAF_DICT_SET, PA_LEAF_RAW_RANGE, PA_LEAF_MV_DICT_RANGE, PA_LEAF_MV_DICT_SET, PA_LEAF_RAW_SET = range(6)
 PA_OP_LEAF, PA_OP_AND, PA_OP_OR, PA_OP_NOT = range(4)
 PA_AGG_COUNT, PA_AGG_SUM, PA_AGG_MIN, PA_AGG_MAX, PA_AGG_DISTINCTCOUNTHLL, PA_AGG_COUNT_MV, PA_AGG_DISTINCTCOUNT, \
-    PA_AGG_VALUE_HISTOGRAM, PA_AGG_LAST_ROW_BY_TIME, PA_AGG_FIRST_ROW_BY_TIME = range(10)
+    PA_AGG_VALUE_HISTOGRAM, PA_AGG_LAST_ROW_BY_TIME, PA_AGG_FIRST_ROW_BY_TIME, PA_AGG_MOMENTS = range(11)
 PA_QF_STAGE_ALL = 1
 PA_QF_FORCE_GLOBAL = 2
 PA_QF_STEPS16 = 1 << 4
@@ -61,7 +61,9 @@ PA_BIT_AND, PA_BIT_OR, PA_BIT_NOT = -1, -2, -3
 PA_BIT_PROG_MAX = 64
 PA_ACC_COUNT_U64, PA_ACC_SUM_I64, PA_ACC_SUM_F64, PA_ACC_MIN_I64, PA_ACC_MAX_I64, PA_ACC_HLL_U8, \
     PA_ACC_SUM_I64X2, PA_ACC_DOCS_U64, PA_ACC_KEYS_I64, PA_ACC_PRESENCE_U8, PA_ACC_HIST_U64, PA_ACC_KEYBITS_U32, \
-    PA_ACC_LANE_COUNT_U64, PA_ACC_TIME_ROW_U64, PA_ACC_TIME_MAX_I64 = range(15)
+    PA_ACC_LANE_COUNT_U64, PA_ACC_TIME_ROW_U64, PA_ACC_TIME_MAX_I64, PA_ACC_MOM_I64, PA_ACC_MOM_F64 = range(17)
+PA_MOMENTS_WORDS = 4
+PA_MOMENTS_FORM_AUTO, PA_MOMENTS_FORM_INTEGER, PA_MOMENTS_FORM_DOUBLE = range(3)
 PA_MAX_PERCENTILES = 64
 PA_TRIM_KEY_COLUMN, PA_TRIM_COUNT, PA_TRIM_AGG, PA_TRIM_AVG, PA_TRIM_RANGE = range(5)
 PA_MAX_TRIM_TERMS = 4
@@ -78,7 +80,7 @@ EXPORTED = [
     "pa_query_selection_segment_docs", "pa_query_selection_counters",
     "pa_query_set_distinct", "pa_query_fetch_distinct",
     "pa_query_set_agg_filters", "pa_query_fetch_lane_counts", "pa_query_lane_docs",
-    "pa_query_set_expressions",
+    "pa_query_set_expressions", "pa_query_set_moments", "pa_query_moments_form", "pa_query_fetch_moments",
     "pa_query_execute", "pa_query_reset", "pa_query_scan", "pa_query_num_eager_literals", "pa_query_lane_major",
     "pa_query_dense_packed", "pa_query_count_free_emit", "pa_query_eq_prefilter", "pa_query_stream_nt",
     "pa_query_eq_jit", "pa_query_partition_keys",
@@ -155,6 +157,15 @@ class AggFilterSpec(ctypes.Structure):
         ("num_ops", ctypes.c_int32 * PA_MAX_AGG_FILTERS),
         ("ops", (ctypes.c_int32 * PA_MAX_OPS) * PA_MAX_AGG_FILTERS),
         ("agg_filter", ctypes.c_int32 * PA_MAX_AGGS),
+    ]
+
+
+class MomentsSpec(ctypes.Structure):
+    _fields_ = [
+        ("second_column", ctypes.c_int32 * PA_MAX_AGGS),
+        ("form", ctypes.c_int32 * PA_MAX_AGGS),
+        ("has_pivot", ctypes.c_int32 * PA_MAX_AGGS),
+        ("pivot", ctypes.c_double * PA_MAX_AGGS),
     ]
 
 
@@ -256,6 +267,9 @@ def _declare(lib):
         "pa_query_percentiles": (ctypes.c_int, [vp, vp, i32, i64, i32, vp, vp]),
         "pa_query_fetch_time_rows": (ctypes.c_int, [vp, vp, i32, i64, i32, vp, vp, vp, vp]),
         "pa_query_time_row_form": (i32, [vp, i32]),
+        "pa_query_set_moments": (ctypes.c_int, [vp, ctypes.POINTER(MomentsSpec)]),
+        "pa_query_moments_form": (ctypes.c_int, [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double)]),
+        "pa_query_fetch_moments": (ctypes.c_int, [vp, vp, i32, i64, vp, vp]),
         "pa_query_matched_docs": (i64, [vp]),
         "pa_query_key_layout": (ctypes.c_int, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32)]),
         "pa_query_limit_trimming": (i32, [vp]),

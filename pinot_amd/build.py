@@ -15,11 +15,11 @@ LIB = os.path.join(HERE, "libpinot_amd.so")
 # slowest first: with fewer cores than units, the long compiles start at once and the short ones fill in behind them
 SOURCES = ["pa_scan_lane_lm.hip", "pa_scan_std.hip", "pa_scan_part_mv.hip", "pa_scan_part_b.hip", "pa_scan_lane_raw.hip",
            "pa_scan_gdense.hip", "pa_scan_global.hip", "pa_scan_lane_dict.hip", "pa_kernels.hip", "pa_scan_part_a.hip",
-           "pa_scan_filtered.hip", "pa_scan_expr.hip", "pa_scan_trow.hip", "pa_stats.hip", "pa_stats_host.hip", "pa_scan_lane_sm.hip", "pa_scan_distinct.hip",
+           "pa_scan_filtered.hip", "pa_scan_expr.hip", "pa_scan_trow.hip", "pa_scan_moments.hip", "pa_stats.hip", "pa_stats_host.hip", "pa_scan_lane_sm.hip", "pa_scan_distinct.hip",
            "pa_scan_select.hip", "pa_plan.hip",
            "pa_jit.hip", "pa_plan_kernels.hip", "pa_select.hip", "pa_distinct.hip", "pa_fetch.hip", "pa_capi.hip",
            "pa_compact.hip", "pa_segment.hip", "pa_hist.hip", "pa_prep.hip", "pa_launch_scan.hip", "pa_merge.hip",
-           "pa_pve.hip", "pa_trim.hip"]
+           "pa_pve.hip", "pa_trim.hip", "pa_moments.hip"]
 # every header under csrc/ (globbed, so a new one is covered without an edit here) and the public C-ABI header
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "pinot_amd.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-munsafe-fp-atomics", "-std=c++17",

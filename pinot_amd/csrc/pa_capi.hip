@@ -111,6 +111,30 @@ int pa_query_set_expressions(pa_query* q, const pa_expr_spec* spec) {
   return PA_OK;
 }
 
+int pa_query_set_moments(pa_query* q, const pa_moments_spec* spec) {
+  if (!q || !spec) return fail(PA_EINVAL, "null query or moments spec");
+  if (q->prepared) return fail(PA_EINVAL, "query already prepared");
+  if (q->is_select || q->is_distinct) return fail(PA_EINVAL, "moments on a selection or distinct query");
+  for (int a = 0; a < q->spec.num_aggs; ++a) {
+    if (q->spec.aggs[a].type != PA_AGG_MOMENTS) continue;
+    if (spec->form[a] < PA_MOMENTS_FORM_AUTO || spec->form[a] > PA_MOMENTS_FORM_DOUBLE)
+      return fail(PA_EINVAL, "moments: bad form");
+    if (spec->has_pivot[a] && !std::isfinite(spec->pivot[a])) return fail(PA_EINVAL, "moments: the pivot must be finite");
+    if (spec->has_pivot[a] && spec->second_column[a] >= 0) return fail(PA_EINVAL, "moments: a covariance takes no pivot");
+  }
+  q->mom_spec = *spec;
+  q->mom_spec_set = true;
+  return PA_OK;
+}
+
+int pa_query_moments_form(const pa_query* q, int32_t agg, int32_t* out_form, double* out_pivot) {
+  if (!q || !q->prepared || agg < 0 || agg >= q->spec.num_aggs || !q->mom_form[agg])
+    return fail(PA_EINVAL, "not a prepared PA_AGG_MOMENTS aggregation");
+  if (out_form) *out_form = q->mom_form[agg];
+  if (out_pivot) *out_pivot = q->mom_pivot[agg];
+  return PA_OK;
+}
+
 int pa_query_lane_docs(pa_query* q, int64_t* out) {
   if (!q || !q->prepared || !out) return fail(PA_EINVAL, "query not prepared");
   if (!q->is_filtered) return fail(PA_EINVAL, "not a query with aggregation filters");
@@ -206,11 +230,12 @@ int pa_query_prepare(pa_query* q) {
   if (!rc) rc = plan_key_space(q, P);
   if (!rc) rc = plan_limit(q, P);
   // (a distinct query and a query with aggregation filters have their own two strategies each)
-  if (!rc && !q->is_distinct && !q->is_filtered && !q->is_expr && !q->is_trow) rc = plan_gdense(q, P);
+  if (!rc && !q->is_distinct && !q->is_filtered && !q->is_expr && !q->is_trow && !q->is_moments) rc = plan_gdense(q, P);
   if (!rc) rc = build_segments(q, P);
   if (!rc && q->is_filtered) rc = filtered_validate(q, P);
   if (!rc && q->is_expr) rc = expr_validate(q, P);
   if (!rc) rc = trow_validate(q, P);
+  if (!rc) rc = mom_validate(q, P);
   if (!rc) rc = plan_walk(q, P);
   if (!rc) rc = plan_accumulators(q, P);
   TilePlan plan, count_plan;
@@ -243,6 +268,10 @@ int pa_query_prepare(pa_query* q) {
   }
   if (q->is_trow) {
     rc = trow_plan(q);
+    if (rc) return rc;
+  }
+  if (q->is_moments) {
+    rc = mom_plan(q);
     if (rc) return rc;
   }
   rc = plan_leaps(q, P);

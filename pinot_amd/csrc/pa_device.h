@@ -72,8 +72,13 @@ enum Strategy : int32_t {
   // FIRSTWITHTIME / LASTWITHTIME (PA_AGG_*_ROW_BY_TIME): filter + per group a 64-bit max of a synthesized (time, row)
   // word next to the ordinary aggregations (pa_strat_trow.h "row by time"): workgroup-private accumulators in LDS,
   // flushed once per workgroup, or device-scope atomics; the wide form launches the scan twice (DevQuery::trow_pass)
-  STRAT_TROW_LDS = 135, STRAT_TROW = 136
+  STRAT_TROW_LDS = 135, STRAT_TROW = 136,
+  // VAR_POP / STDDEV / COVAR (PA_AGG_MOMENTS): filter + per group the moment sums (exact integers or pivoted doubles)
+  // next to the ordinary aggregations (pa_strat_moments.h "moments"): workgroup-private accumulators in LDS, flushed
+  // once per workgroup, or device-scope atomics
+  STRAT_MOM_LDS = 137, STRAT_MOM = 138
 };
+__host__ __device__ constexpr bool is_mom(int s) { return s == STRAT_MOM_LDS || s == STRAT_MOM; }
 __host__ __device__ constexpr bool is_trow(int s) { return s == STRAT_TROW_LDS || s == STRAT_TROW; }
 __host__ __device__ constexpr bool is_trow_agg(int type) {
   return type == PA_AGG_LAST_ROW_BY_TIME || type == PA_AGG_FIRST_ROW_BY_TIME;
@@ -83,7 +88,7 @@ __host__ __device__ constexpr bool is_filtered(int s) { return s == STRAT_FILTER
 // strategies whose accumulators (Acc<STRAT>) are the workgroup's LDS copies
 __host__ __device__ constexpr bool is_expr(int s) { return s == STRAT_EXPR_LDS || s == STRAT_EXPR; }
 __host__ __device__ constexpr bool acc_in_lds(int s) {
-  return s == STRAT_LDS || s == STRAT_FILTERED_LDS || s == STRAT_EXPR_LDS || s == STRAT_TROW_LDS;
+  return s == STRAT_LDS || s == STRAT_FILTERED_LDS || s == STRAT_EXPR_LDS || s == STRAT_TROW_LDS || s == STRAT_MOM_LDS;
 }
 __host__ __device__ constexpr bool is_pcount(int s) { return s == STRAT_PCOUNT || s == STRAT_PCOUNT_MV; }
 // STRAT_GDENSE: 4-wave workgroups; STRAT_GDENSE8 / STRAT_GDENSE12: the same kernel with 8- / 12-wave workgroups (2 / 3
@@ -362,6 +367,18 @@ struct DevQuery {
   // aggregation, no numDocsScanned (the planner gives such a query no fused filter statistics)
   const struct TrowDesc* trow;
   int32_t trow_pass, pad_trow;
+  const struct MomDesc* mom;     // moments (STRAT_MOM*): every PA_AGG_MOMENTS aggregation's form, pivot and second column
+};
+// ---------------------------------------------------------------- moments (STRAT_MOM_LDS / STRAT_MOM)
+// PA_AGG_MOMENTS aggregation a (pa_strat_moments.h "moments"), wave-uniform. Per key PA_MOMENTS_WORDS 64-bit words at
+// DevAgg::acc_i64 + key * PA_MOMENTS_WORDS (pinot_amd.h PA_ACC_MOM_I64 / PA_ACC_MOM_F64 gives their meaning).
+struct MomAgg {
+  double pivot;   // double form, variance: d = x - pivot (0 otherwise)
+  int32_t slot2;  // covariance: the second column's slot; -1 = variance
+  int32_t form;   // PA_MOMENTS_FORM_INTEGER / PA_MOMENTS_FORM_DOUBLE
+};
+struct MomDesc {
+  MomAgg agg[PA_MAX_AGGS];
 };
 // ---------------------------------------------------------------- row by time (STRAT_TROW_LDS / STRAT_TROW)
 // PA_AGG_LAST / FIRST_ROW_BY_TIME aggregation a (pa_strat_trow.h "row by time"). x = the doc's time: the raw INT / LONG

@@ -99,6 +99,7 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
           const pa_agg_spec& A = s.aggs[a];
           if (A.type == PA_AGG_VALUE_HISTOGRAM) continue;  // 0 bytes per row: pa_query_fetch_histogram reads the bins
           if (time_row_agg(A.type)) continue;              // 0 bytes per row: pa_query_fetch_time_rows reads the rows
+          if (moments_agg(A.type)) continue;               // 0 bytes per row: pa_query_fetch_moments reads the tuples
           double* outd = (double*)out_aggs[a];
           if (A.type == PA_AGG_COUNT) {
             outd[n] = (double)hc[r];
@@ -202,11 +203,12 @@ int64_t pa_query_fetch(pa_query* q, void* stream, int64_t capacity, int64_t* out
     size_t bytes = ((size_t)rows_cap * 16 + 255) & ~(size_t)255;  // keys | counts
     for (int a = 0; a < s.num_aggs; ++a) {
       const pa_agg_spec& A = s.aggs[a];
-      f.type[a] = A.type;
+      // (a PA_AGG_MOMENTS aggregation goes to the kernel as the other type with 0 bytes per row: it skips both alike)
+      f.type[a] = moments_agg(A.type) ? PA_AGG_VALUE_HISTOGRAM : A.type;
       f.src[a] = q->hq.aggs[a].src;
       f.sec[a] = q->agg_section[a] >= 0 ? q->sections[q->agg_section[a]].ptr : nullptr;
       f.per[a] = A.type == PA_AGG_DISTINCTCOUNT ? presence_stride(A)
-                 : (A.type == PA_AGG_VALUE_HISTOGRAM || time_row_agg(A.type)) ? 0  // (nothing staged or copied)
+                 : (A.type == PA_AGG_VALUE_HISTOGRAM || time_row_agg(A.type) || moments_agg(A.type)) ? 0  // (nothing staged or copied)
                  : (A.type == PA_AGG_DISTINCTCOUNTHLL ? (int64_t(1) << A.log2m) : 8);
       off[a] = bytes;
       bytes += ((size_t)rows_cap * (size_t)f.per[a] + 255) & ~(size_t)255;
@@ -318,6 +320,9 @@ int64_t pa_query_fetch_trimmed(pa_query* q, void* stream, const pa_trim_spec* sp
   for (int a = 0; a < s.num_aggs; ++a)
     if (time_row_agg(s.aggs[a].type))
       return fail(PA_EUNSUPPORTED, "device group trim: the query has a LAST / FIRST_ROW_BY_TIME aggregation");
+  for (int a = 0; a < s.num_aggs; ++a)
+    if (moments_agg(s.aggs[a].type))
+      return fail(PA_EUNSUPPORTED, "device group trim: the query has a PA_AGG_MOMENTS aggregation");
   if (spec->num_terms < 0) return fail(PA_EINVAL, "fetch trimmed: negative term count");
   if (spec->num_terms > PA_MAX_TRIM_TERMS) return fail(PA_EUNSUPPORTED, "device group trim: too many ORDER BY terms");
   const int64_t K = q->num_keys;

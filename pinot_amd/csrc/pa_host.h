@@ -96,6 +96,10 @@ struct Column {
   bool dict_sorted = false; // dictionary values strictly ascending (COLF_DICT_SORTED)
   bool has_raw_minmax = false;  // raw INT / LONG column with docs: raw_min / raw_max hold its smallest / largest value
   int64_t raw_min = 0, raw_max = 0;
+  // raw column of any numeric type with a value that is not NaN: its smallest / largest such value as doubles (the
+  // moments' pivot, pa_plan.hip mom_validate)
+  bool has_val_minmax = false;
+  double val_min = 0.0, val_max = 0.0;
   std::vector<uint64_t> hvals;  // host copy of the dictionary values (8-byte bits): table-wide value dictionaries
   uint64_t dict_hash = 0;       // FNV-1a of hvals: identical dictionaries across segments are found without a compare
   DevBuf words;   // guard + stream + pad (SV dict)
@@ -204,6 +208,8 @@ inline int64_t hist_stride(const pa_agg_spec& A) { return (A.num_values + 1) & ~
 inline bool value_id_agg(int32_t type) { return type == PA_AGG_DISTINCTCOUNT || type == PA_AGG_VALUE_HISTOGRAM; }
 // FIRSTWITHTIME / LASTWITHTIME: the per-group winning row (pa_strat_trow.h)
 inline bool time_row_agg(int32_t type) { return type == PA_AGG_LAST_ROW_BY_TIME || type == PA_AGG_FIRST_ROW_BY_TIME; }
+// VAR_POP / STDDEV / COVAR: the per-group moment sums (pa_strat_moments.h)
+inline bool moments_agg(int32_t type) { return type == PA_AGG_MOMENTS; }
 // element bytes of an accumulator section
 inline size_t section_es(int32_t kind) {
   return (kind == PA_ACC_HLL_U8 || kind == PA_ACC_PRESENCE_U8) ? 1 : (kind == PA_ACC_KEYBITS_U32 ? 4 : 8);
@@ -370,8 +376,21 @@ struct pa_query {
   int64_t trow_tmin[PA_MAX_AGGS] = {0};     // packed, raw time column: the bound segments' smallest time
   TrowDesc htrow{};
   DevBuf dq_pass2, trow_desc, trow_buf;
+  // VAR_POP / STDDEV / COVAR (PA_AGG_MOMENTS; pa_strat_moments.h "moments"): the caller's spec (pa_query_set_moments), per
+  // aggregation its form (0 = not such an aggregation, else PA_MOMENTS_FORM_INTEGER / _DOUBLE), pivot and second
+  // column's slot (-1 = variance), the scan's descriptor and the finish kernel's buffer
+  bool is_moments = false;
+  bool mom_spec_set = false;
+  pa_moments_spec mom_spec{};
+  int mom_form[PA_MAX_AGGS] = {0};
+  double mom_pivot[PA_MAX_AGGS] = {0};
+  int mom_slot2[PA_MAX_AGGS] = {0};
+  MomDesc hmom{};
+  DevBuf mom_desc, mom_buf;
 
   ~pa_query() {
+    dev_free(mom_desc);
+    dev_free(mom_buf);
     dev_free(dq_pass2);
     dev_free(trow_desc);
     dev_free(trow_buf);
@@ -493,6 +512,8 @@ int expr_validate(pa_query* q, Prep& P);            // prepare, after build_segm
 int expr_plan(pa_query* q, const Prep& P);          // prepare, after fill_devquery: the programs' descriptor, uploaded
 int trow_validate(pa_query* q, Prep& P);            // prepare, after build_segments: what a row-by-time query refuses
 int trow_plan(pa_query* q);                         // prepare, after fill_devquery: the words' layout; the second descriptor
+int mom_validate(pa_query* q, Prep& P);             // prepare, after build_segments: what a moments query refuses; forms, pivots
+int mom_plan(pa_query* q);                          // prepare, after fill_devquery: the moments' descriptor, uploaded
 int mv_group_component(const pa_query* q);
 int plan_filter(pa_query* q, Prep& P);
 int plan_slots(pa_query* q, Prep& P);

@@ -636,7 +636,7 @@ int eqs_plan(pa_query* q, const Prep& P, int cus) {
   if (tn.eq_jit == 0 || (s.flags & (PA_QF_NO_JIT | PA_QF_DEBUG_STREAM_ONLY)) || tn.debug_emit) return PA_OK;
   if (q->nseg == 0 || q->num_tiles == 0 || q->num_tiles >= (uint64_t(1) << 31) || q->strategy != STRAT_GLOBAL || !q->lane_major || q->steps != 32 ||
       q->hashed || q->partitioned || q->limit_mode || q->limit_walk || q->has_mv || h.gb_mv >= 0 || q->is_select ||
-      q->is_distinct || q->is_filtered || q->is_expr || q->is_trow)
+      q->is_distinct || q->is_filtered || q->is_expr || q->is_trow || q->is_moments)
     return PA_OK;
   const int nl = (int)q->literals.size(), ng = s.num_group_by;
   if (nl < 1 || nl - 1 > kJitMax || q->num_eager < 1 || ng > kJitMaxGb || h.num_gb != ng) return PA_OK;

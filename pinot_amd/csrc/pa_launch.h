@@ -276,6 +276,7 @@ const void* scan_fn_distinct(int strategy, int steps);     // pa_scan_distinct.h
 const void* scan_fn_filtered(int strategy, int steps);     // pa_scan_filtered.hip: STRAT_FILTERED* (step-major tiles)
 const void* scan_fn_expr(int strategy, int steps);         // pa_scan_expr.hip: STRAT_EXPR* (step-major tiles)
 const void* scan_fn_trow(int strategy, int steps);         // pa_scan_trow.hip: STRAT_TROW* (step-major tiles)
+const void* scan_fn_moments(int strategy, int steps);      // pa_scan_moments.hip: STRAT_MOM* (step-major tiles)
 hipError_t set_scan_lds_limit(int strategy, int steps, int lm, int bytes);
 hipError_t scan_occupancy(int strategy, int steps, int lm, int lds_bytes, int* blocks_per_cu);
 hipError_t launch_scan(int strategy, int steps, int lm, int grid, int lds_bytes, const DevQuery* q, const DevSeg* segs,

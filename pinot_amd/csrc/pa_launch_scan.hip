@@ -14,6 +14,7 @@ static const void* scan_fn(int strategy, int steps, int lm) {
   if (const void* f = scan_fn_filtered(strategy, steps)) return f;
   if (const void* f = scan_fn_expr(strategy, steps)) return f;
   if (const void* f = scan_fn_trow(strategy, steps)) return f;
+  if (const void* f = scan_fn_moments(strategy, steps)) return f;
   if (const void* f = scan_fn_part_a(strategy)) return f;
   if (const void* f = scan_fn_part_mv(strategy)) return f;
   return scan_fn_part_b(strategy);

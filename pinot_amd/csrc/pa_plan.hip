@@ -203,11 +203,22 @@ int plan_slots(pa_query* q, Prep& P) {
   }
   P.agg_slot.assign(s.num_aggs, 0);
   q->is_trow = false;
+  q->is_moments = false;
   for (int a = 0; a < s.num_aggs; ++a) {
     const int t = s.aggs[a].type;
-    if (t < PA_AGG_COUNT || t > PA_AGG_FIRST_ROW_BY_TIME) return fail(PA_EINVAL, "bad aggregation type");
+    if (t < PA_AGG_COUNT || t > PA_AGG_MOMENTS) return fail(PA_EINVAL, "bad aggregation type");
+    q->mom_slot2[a] = -1;
     if (t == PA_AGG_COUNT) continue;
     if (time_row_agg(t)) q->is_trow = true;
+    if (moments_agg(t)) {
+      q->is_moments = true;
+      // (a covariance's second column: a post-filter column like the first)
+      const int32_t c2 = q->mom_spec_set ? q->mom_spec.second_column[a] : -1;
+      if (c2 >= 0) {
+        q->mom_slot2[a] = slot_of(q, c2);
+        if (q->mom_slot2[a] < 0) return fail(PA_EUNSUPPORTED, "too many distinct columns in one query");
+      }
+    }
     P.agg_slot[a] = slot_of(q, s.aggs[a].column_id);
     if (P.agg_slot[a] < 0) return fail(PA_EUNSUPPORTED, "too many distinct columns in one query");
     if (t == PA_AGG_DISTINCTCOUNTHLL && (s.aggs[a].log2m < 4 || s.aggs[a].log2m > 16))
@@ -226,6 +237,8 @@ int plan_slots(pa_query* q, Prep& P) {
   for (int j = 0; j < s.num_group_by; ++j) P.slot_post[P.gb_slot[j]] = 1;
   for (int a = 0; a < s.num_aggs; ++a)
     if (s.aggs[a].type != PA_AGG_COUNT) P.slot_post[P.agg_slot[a]] = 1;
+  for (int a = 0; a < s.num_aggs; ++a)
+    if (q->mom_slot2[a] >= 0) P.slot_post[q->mom_slot2[a]] = 1;
   // (the aggregation filters run on the docs the query's own filter kept: their columns are post-filter columns)
   for (const std::vector<Literal>& lits : q->filt_lits)
     for (const Literal& lit : lits) P.slot_post[P.leaf_slot[lit.leaf]] = 1;
@@ -991,6 +1004,11 @@ int build_segments(pa_query* q, Prep& P) {
         P.val_fast[a] = 0;
         continue;
       }
+      if (moments_agg(A.type)) {  // (mom_validate checks the argument columns and picks the form)
+        P.agg_src[a] = SRC_LONG;
+        P.val_fast[a] = 0;
+        continue;
+      }
       if (value_id_agg(A.type)) {
         const bool hist = A.type == PA_AGG_VALUE_HISTOGRAM;
         if (c->kind != COL_SV_DICT && c->kind != COL_MV_DICT)
@@ -1090,6 +1108,10 @@ int plan_accumulators(pa_query* q, Prep& P) {
         }
         sec.push_back({PA_ACC_TIME_ROW_U64, K});
         break;
+      case PA_AGG_MOMENTS:
+        if (K > INT64_MAX / 8 / PA_MOMENTS_WORDS) return fail(PA_ENOMEM, "moments: too many keys");
+        sec.push_back({q->mom_form[a] == PA_MOMENTS_FORM_INTEGER ? PA_ACC_MOM_I64 : PA_ACC_MOM_F64, K * PA_MOMENTS_WORDS});
+        break;
     }
     q->agg_section[a] = (int)sec.size() - 1;
   }
@@ -1126,6 +1148,7 @@ int plan_accumulators(pa_query* q, Prep& P) {
     const size_t bytes = A.type == PA_AGG_DISTINCTCOUNTHLL ? ((size_t)K << A.log2m) * 4
                          : A.type == PA_AGG_DISTINCTCOUNT ? (size_t)K * presence_stride(A)
                          : A.type == PA_AGG_VALUE_HISTOGRAM ? (size_t)K * hist_stride(A) * 4  // WG-private u32 bins
+                         : A.type == PA_AGG_MOMENTS ? (size_t)K * 8 * PA_MOMENTS_WORDS
                          : (size_t)K * 8 * ((A.type == PA_AGG_SUM && P.agg_src[a] == SRC_LONG) ? 2 : 1);
     P.lds_acc += (bytes + 15) & ~(size_t)15;
   }
@@ -1381,6 +1404,105 @@ int trow_plan(pa_query* q) {
   PA_HIP(hipMemcpy(q->trow_desc.p, &T, sizeof(T), hipMemcpyHostToDevice));
   q->hq.trow = (const TrowDesc*)q->trow_desc.p;
   q->hq.trow_pass = q->trow_wide ? 1 : 0;
+  return PA_OK;
+}
+
+// A query with PA_AGG_MOMENTS aggregations against what the moment strategies cover (pa_strat_moments.h "moments"), and
+// every such aggregation's form and pivot: the integer form where every argument column is INT / LONG with all values
+// inside int32 in every bound segment, else the double form; a variance's pivot there is the midpoint of the column's
+// smallest and largest value over the bound segments (dictionary values, or the raw column's metadata; NaN ignored),
+// 0 where that is not finite. pa_query_set_moments overrides both (ranks of a multi-GPU query pass agreed values).
+int mom_validate(pa_query* q, Prep& P) {
+  const pa_query_spec& s = q->spec;
+  for (int a = 0; a < PA_MAX_AGGS; ++a) {
+    q->mom_form[a] = 0;
+    q->mom_pivot[a] = 0.0;
+  }
+  if (q->is_select || q->is_distinct) q->is_moments = false;  // (their spec's aggregations are not computed)
+  if (!q->is_moments) return PA_OK;
+  const char* fn = "VAR_POP / STDDEV / COVAR";
+  if (q->is_filtered)
+    return fail(PA_EUNSUPPORTED, std::string(fn) + " in a query with aggregation filters is not supported");
+  if (q->is_expr) return fail(PA_EUNSUPPORTED, std::string(fn) + " next to transform expressions is not supported");
+  if (q->is_trow) return fail(PA_EUNSUPPORTED, std::string(fn) + " next to FIRSTWITHTIME / LASTWITHTIME is not supported");
+  if (q->hashed)
+    return fail(PA_EUNSUPPORTED, std::string(fn) + " over a hashed key space (a raw group-by column, or a product of "
+                                                   "group-by cardinalities too large to address directly) is not supported");
+  if (q->limit_mode)
+    return fail(PA_EUNSUPPORTED, std::string(fn) + " where numGroupsLimit trimming runs its first-position + sort passes "
+                                                   "is not supported (the prefix walk is)");
+  if (q->has_mv || P.gb_mv)
+    return fail(PA_EUNSUPPORTED, std::string(fn) + " next to a multi-value group-by or aggregation column is not supported");
+  for (int a = 0; a < s.num_aggs; ++a) {
+    const pa_agg_spec& A = s.aggs[a];
+    if (!moments_agg(A.type)) continue;
+    const int32_t c2 = q->mom_spec_set ? q->mom_spec.second_column[a] : -1;
+    const bool cov = c2 >= 0;
+    bool integer = true, any = false;
+    double lo = 0.0, hi = 0.0;
+    for (int ci = 0; ci < (cov ? 2 : 1); ++ci) {
+      const int32_t cid = ci == 0 ? A.column_id : c2;
+      for (int si = 0; si < q->nseg; ++si) {
+        auto it = q->segs[si]->cols.find(cid);
+        if (it == q->segs[si]->cols.end()) return fail(PA_EINVAL, "moments: argument column missing in a segment");
+        const Column* c = it->second;
+        if (c->kind != COL_SV_DICT && c->kind != COL_SV_RAW)
+          return fail(PA_EUNSUPPORTED, std::string(fn) + ": a multi-value argument column is not supported");
+        if (c->vtype == PA_STRING || c->vtype == PA_BYTES)
+          return fail(PA_EUNSUPPORTED, std::string(fn) + ": a STRING / BYTES argument column is not supported");
+        if (c->kind == COL_SV_DICT && !c->dict.p) return fail(PA_EINVAL, "dictionary values missing");
+        const bool is_int = c->vtype == PA_INT || c->vtype == PA_LONG;
+        if (!is_int || !c->fits_int32) integer = false;
+        if (cov) continue;  // (no pivot)
+        if (c->kind == COL_SV_DICT) {
+          for (uint64_t bits : c->hvals) {
+            double x;
+            if (is_int) {
+              x = (double)(int64_t)bits;
+            } else {
+              std::memcpy(&x, &bits, 8);
+              if (x != x) continue;
+            }
+            lo = !any || x < lo ? x : lo;
+            hi = !any || x > hi ? x : hi;
+            any = true;
+          }
+        } else if (c->has_val_minmax) {
+          lo = !any || c->val_min < lo ? c->val_min : lo;
+          hi = !any || c->val_max > hi ? c->val_max : hi;
+          any = true;
+        }
+      }
+    }
+    const int32_t forced = q->mom_spec_set ? q->mom_spec.form[a] : PA_MOMENTS_FORM_AUTO;
+    if (forced == PA_MOMENTS_FORM_INTEGER && !integer)
+      return fail(PA_EINVAL, "moments: the integer form needs INT / LONG argument columns with every value inside int32");
+    q->mom_form[a] = forced != PA_MOMENTS_FORM_AUTO ? forced : (integer ? PA_MOMENTS_FORM_INTEGER : PA_MOMENTS_FORM_DOUBLE);
+    if (q->mom_form[a] == PA_MOMENTS_FORM_DOUBLE && !cov) {
+      double pivot = any ? lo / 2 + hi / 2 : 0.0;  // (halves first: the midpoint of +-DBL_MAX is finite)
+      if (!std::isfinite(pivot)) pivot = 0.0;
+      if (q->mom_spec_set && q->mom_spec.has_pivot[a]) pivot = q->mom_spec.pivot[a];
+      q->mom_pivot[a] = pivot;
+    }
+  }
+  return PA_OK;
+}
+
+// The moments' descriptor, uploaded (after fill_devquery).
+int mom_plan(pa_query* q) {
+  MomDesc& M = q->hmom;
+  std::memset(&M, 0, sizeof(M));
+  for (int a = 0; a < q->spec.num_aggs; ++a) {
+    M.agg[a].slot2 = q->mom_slot2[a];
+    M.agg[a].form = q->mom_form[a];
+    M.agg[a].pivot = q->mom_pivot[a];
+  }
+  if (!q->mom_desc.p) {
+    int rc = dev_alloc(q->mom_desc, sizeof(MomDesc));
+    if (rc) return rc;
+  }
+  PA_HIP(hipMemcpy(q->mom_desc.p, &M, sizeof(M), hipMemcpyHostToDevice));
+  q->hq.mom = (const MomDesc*)q->mom_desc.p;
   return PA_OK;
 }
 

@@ -572,6 +572,35 @@ int plan_kernels(pa_query* q, Prep& P, TilePlan& plan, TilePlan& count_plan) {
     q->dma_slots = plan.dma;
     return PA_OK;
   }
+  if (q->is_moments) {
+    // Moments (VAR_POP / STDDEV / COVAR): the step-major scan with the strategies of pa_strat_moments.h; the per-lane
+    // aggregation-only strategies, the dense / JIT kernel and the partitioned plan do not hold the update (an
+    // aggregation-only query runs with one key). Workgroup-private LDS accumulators by STRAT_LDS's rule — the block takes
+    // at most 64 KiB next to the tile ring, and dense matches — else device-scope atomics. PA_QF_FORCE_LDS /
+    // PA_QF_FORCE_GLOBAL act as on STRAT_LDS; tuning moments_lds forces either (1: whenever the block fits at all).
+    q->partitioned = false;
+    P.lm = false;
+    plan = TilePlan{};
+    const int force = q->tune.moments_lds;
+    const bool want_lds = force < 0 ? (!(s.flags & PA_QF_FORCE_GLOBAL) &&
+                                       ((s.flags & PA_QF_FORCE_LDS) ? P.lds_acc < kLdsBudget
+                                                                    : (P.lds_acc <= 64 * 1024 && P.dense)))
+                                    : (force == 1 && P.lds_acc < kLdsBudget);
+    if (want_lds) plan = plan_tiles(q, q->hsegs, STRAT_MOM_LDS, false, P.lds_acc, false);
+    if (plan.score >= 0) {
+      q->strategy = STRAT_MOM_LDS;
+    } else {
+      q->strategy = STRAT_MOM;
+      P.lds_acc = 0;
+      plan = plan_tiles(q, q->hsegs, STRAT_MOM, false, 0, false);
+    }
+    if (plan.score < 0) return fail(PA_EUNSUPPORTED, "staged columns too wide for the LDS tile ring");
+    PLAN_LOG("moments: K=%lld %s accumulators", (long long)K, q->strategy == STRAT_MOM_LDS ? "LDS" : "global");
+    q->lds_bytes = (int)plan.lds;
+    q->steps = plan.steps;
+    q->dma_slots = plan.dma;
+    return PA_OK;
+  }
   // Lane-major kernel: every eager literal is a dictionary leaf on a staged column and the per-segment plan table
   // has room for the staged columns and eager literals (otherwise the step-major kernel runs the query).
   bool lm = !(s.flags & (PA_QF_NO_LANE_MAJOR | PA_QF_STEPS16)) && q->num_eager <= kLmEager;
@@ -900,7 +929,7 @@ void fill_devquery(pa_query* q, const Prep& P, const TilePlan& plan, int64_t tot
   h.keybits = q->is_distinct ? (uint32_t*)q->sections[0].ptr : nullptr;
   h.lds_acc_bytes = (q->strategy == STRAT_LDS || is_gdense(q->strategy) || is_lane(q->strategy) || q->strategy == STRAT_SELECT ||
                      q->strategy == STRAT_DISTINCT_LDS || q->strategy == STRAT_FILTERED_LDS || q->strategy == STRAT_EXPR_LDS ||
-                     q->strategy == STRAT_TROW_LDS)
+                     q->strategy == STRAT_TROW_LDS || q->strategy == STRAT_MOM_LDS)
                         ? (uint32_t)P.lds_acc : 0;
   if (is_gdense(q->strategy)) {
     // per-segment parameter tables (GdSegPlan): the query's key box and LDS layout + the segment's staged regions
@@ -1291,6 +1320,7 @@ int plan_leaps(pa_query* q, const Prep& P) {
   if (q->partitioned || q->limit_mode || q->limit_walk || is_gdense(q->strategy)) return PA_OK;
   if (q->is_filtered) return PA_OK;  // (its statistics come from the lanes' doc counts: pa_query_lane_docs)
   if (q->is_trow) return PA_OK;      // (the wide form runs the tile loop twice; both forms take the bitmap path)
+  if (q->is_moments) return PA_OK;   // (the bitmap path answers the filter statistics)
   if (P.first_clause_sel > 1.0 / 256.0) return PA_OK;
   q->hq.leap_mode = 1;
   q->leap_leaf = q->literals[0].leaf;

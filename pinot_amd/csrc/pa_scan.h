@@ -1361,6 +1361,15 @@ template <int WGS>
 __device__ __forceinline__ void trow_lds_zero(const DevQuery* q, unsigned char* lds_acc);
 template <int WGS>
 __device__ __forceinline__ void trow_lds_flush(const DevQuery* q, unsigned char* lds_acc);
+// pa_strat_moments.h
+template <int STRAT>
+__device__ __forceinline__ void mom_step(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
+                                         const uint32_t* img, int doc_local, int64_t doc, uint64_t matched, int lane,
+                                         const Acc<STRAT>& acc);
+template <int WGS>
+__device__ __forceinline__ void mom_lds_zero(const DevQuery* q, unsigned char* lds_acc);
+template <int WGS>
+__device__ __forceinline__ void mom_lds_flush(const DevQuery* q, unsigned char* lds_acc);
 // pa_strat_part.h
 template <int STRAT, int STEPS, int LM>
 __device__ __forceinline__ void part_tile(const DevQuery* __restrict__ q, const DevSeg* __restrict__ seg,
@@ -1440,6 +1449,13 @@ __device__ __forceinline__ uint32_t tile_survivors(const DevQuery* __restrict__ 
       const uint64_t sm = __ballot((m >> i) & 1u);
       if (sm == 0) continue;
       trow_step<STRAT>(q, seg, img, i * kWave + lane, doc_base + i * kWave + lane, sm, lane, acc);
+    }
+  } else if constexpr (is_mom(STRAT)) {
+    static_assert(!LM, "moment queries run step-major tiles");
+    for (int i = 0; i < STEPS; ++i) {
+      const uint64_t sm = __ballot((m >> i) & 1u);
+      if (sm == 0) continue;
+      mom_step<STRAT>(q, seg, img, i * kWave + lane, doc_base + i * kWave + lane, sm, lane, acc);
     }
   } else if constexpr (is_lane(STRAT)) {
     if constexpr (STRAT != STRAT_LANE_CNT) lane_acc_tile<LM, STEPS, STRAT>(q, seg, img, doc_base, m, lane, la, lds);
@@ -1775,6 +1791,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_EXPR_LDS) lds_acc_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_TROW_LDS) trow_lds_zero<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_MOM_LDS) mom_lds_zero<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_LANE_DICT) lane_hist_zero<WGS>(q, lds_acc);
   const int64_t T = q->total_wtiles;
   const int64_t W = (int64_t)gridDim.x * WPW;
@@ -1932,6 +1949,7 @@ __global__ void __launch_bounds__(scan_waves(STRAT) * kWave, emit_v_wide(STRAT) 
   if constexpr (STRAT == STRAT_FILTERED_LDS) filtered_lds_flush<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_EXPR_LDS) lds_acc_flush<WGS>(q, lds_acc);
   if constexpr (STRAT == STRAT_TROW_LDS) trow_lds_flush<WGS>(q, lds_acc);
+  if constexpr (STRAT == STRAT_MOM_LDS) mom_lds_flush<WGS>(q, lds_acc);
   if constexpr (is_trow(STRAT)) {  // (the wide form's second launch sees the docs the first counted)
     if (q->trow_pass == 2) matched = 0;
   }

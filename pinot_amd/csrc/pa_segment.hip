@@ -217,6 +217,23 @@ int pa_segment_add_raw_column(pa_segment* seg, int32_t column_id, int32_t value_
     c->raw_max = hi;
     c->has_raw_minmax = true;
   }
+  {  // (column metadata min/max of every numeric type as doubles, NaN ignored: the moments' pivot)
+    double lo = 0.0, hi = 0.0;
+    bool any = false;
+    for (int32_t i = 0; i < seg->num_docs; ++i) {
+      const double x = value_type == PA_INT     ? (double)((const int32_t*)values)[i]
+                       : value_type == PA_LONG  ? (double)((const int64_t*)values)[i]
+                       : value_type == PA_FLOAT ? (double)((const float*)values)[i]
+                                                : ((const double*)values)[i];
+      if (x != x) continue;
+      lo = !any || x < lo ? x : lo;
+      hi = !any || x > hi ? x : hi;
+      any = true;
+    }
+    c->has_val_minmax = any;
+    c->val_min = lo;
+    c->val_max = hi;
+  }
   seg->bytes += c->raw.n;
   seg->cols[column_id] = c;
   return PA_OK;

@@ -95,7 +95,11 @@
   /* FIRSTWITHTIME / LASTWITHTIME: 0 = device-scope atomics (STRAT_TROW), 1 = the workgroup-private LDS accumulators    \
      (STRAT_TROW_LDS) whenever they fit next to a tile ring (default: when they take at most 64 KiB and the matching    \
      docs are dense, STRAT_LDS's rule; PA_QF_FORCE_LDS / PA_QF_FORCE_GLOBAL act as on STRAT_LDS) */                    \
-  X(time_rows_lds, -1, 0, 1, 0)
+  X(time_rows_lds, -1, 0, 1, 0)                                                                                        \
+  /* VAR_POP / STDDEV / COVAR: 0 = device-scope atomics (STRAT_MOM), 1 = the workgroup-private LDS accumulators         \
+     (STRAT_MOM_LDS) whenever they fit next to a tile ring (default: when they take at most 64 KiB and the matching     \
+     docs are dense, STRAT_LDS's rule; PA_QF_FORCE_LDS / PA_QF_FORCE_GLOBAL act as on STRAT_LDS) */                    \
+  X(moments_lds, -1, 0, 1, 0)
 
 struct Tuning {
 #define X(name, def, lo, hi, inv) int32_t name = def;

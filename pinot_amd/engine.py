@@ -133,6 +133,25 @@ class ValueTimePair:
         return a == b or (isinstance(a, float) and isinstance(b, float) and a != a and b != b)
 
 
+@dataclass
+class VarianceTuple:
+    """VarianceAggregationFunction intermediate result (VarianceTuple.java: count, sum, m2 = the sum of squared
+    deviations from the mean). The empty tuple is (0, 0.0, 0.0)."""
+    count: int
+    sum: float
+    m2: float
+
+
+@dataclass
+class CovarianceTuple:
+    """CovarianceAggregationFunction intermediate result (CovarianceTuple.java: the raw sums of x, y and x * y, and the
+    count, in the constructor's order). The empty tuple is (0.0, 0.0, 0.0, 0)."""
+    sum_x: float
+    sum_y: float
+    sum_xy: float
+    count: int
+
+
 LONG_MIN, LONG_MAX = -(1 << 63), (1 << 63) - 1
 INT_MIN, INT_MAX = -(1 << 31), (1 << 31) - 1
 
@@ -302,7 +321,7 @@ def _flatten_filter(f, leaves, ops):
 class GpuQueryExecutor:
     def __init__(self, query: Q.Query, gpu_segments: List[GpuSegment], flags=0, enforce_num_groups_limit=True,
                  table_dicts=None, wide_sum_columns=(), value_dicts=None, hash_keys_bound=0, schema=None,
-                 tuning=None):
+                 tuning=None, moments=None):
         """table_dicts: optional {group-by column: sorted unique values} — the table-wide dictionary every rank of a
         multi-GPU query must share so that key ids address the same accumulator rows everywhere
         (parallel.table_layout builds it); by default it is the union of these segments' dictionaries.
@@ -317,13 +336,17 @@ class GpuQueryExecutor:
         every segment given here is empty, the executor plans over a one-doc placeholder segment of that schema and never
         scans it, so the rank still holds a (zero) accumulator block of the agreed layout and joins the cross-GPU merge.
         tuning: optional {name: int} planner overrides of this query (pa_query_set_tuning; csrc/pa_tuning.h lists them):
-        tests and measurement only."""
+        tests and measurement only.
+        moments: optional {(column, second column or None): (form, pivot or None)} — the form (_lib.PA_MOMENTS_FORM_*) and
+        the double form's pivot of a VAR / STDDEV / COVAR accumulator, agreed across ranks by parallel.table_layout
+        (pa_query_set_moments); by default the library chooses both from these segments."""
         if not gpu_segments:
             raise ValueError("no segments")
         self.table_dicts = table_dicts or {}
         self.table_value_dicts = value_dicts or {}
         self.wide_sum_columns = set(wide_sum_columns or ())
         self.hash_keys_bound = int(hash_keys_bound or 0)
+        self.moments = dict(moments or {})
         self.query = query
         # empty segments hold no indexes and contribute nothing but their (zero) doc count: only the others are bound
         self.all_segs = [g.segment for g in gpu_segments]
@@ -430,12 +453,23 @@ class GpuQueryExecutor:
         # transform expressions (SUM(ADD(a, b)), GROUP BY timeConvert(...); transform.py): every distinct expression of
         # the aggregation arguments and group-by items becomes one device program over a shared operand-column table
         # (pa_query_set_expressions). An expression aggregation's GPU accumulator is keyed by column id -2 - its index.
+        for a in q.aggregations:
+            if a.function in Q.MOMENT_FUNCTIONS:
+                self._check_moments(a)
         self.exprs, self.programs, self.expr_columns = T.check_query(
             q, {n: (c.data_type, bool(c.single_value)) for n, c in seg0.columns.items()})
         expr_index = self.exprs.index
 
         for a in q.aggregations:
             fn = a.function
+            if fn in Q.MOMENT_FUNCTIONS:
+                self.agg_lane.append(-1)
+                cur[0] = -1
+                # keyed by the argument column(s): the spellings of one family over the same argument(s) share the
+                # accumulator (third field: the covariance's second column id, -1 = variance)
+                self.agg_map.append(acc_index((L.PA_AGG_MOMENTS, ids[a.column],
+                                               ids[a.column2] if a.column2 is not None else -1)))
+                continue
             if isinstance(a.column, Q.Expr):
                 cid = -2 - expr_index(a.column)
                 self.agg_lane.append(-1)
@@ -513,7 +547,7 @@ class GpuQueryExecutor:
         for i, (t, cid, log2m) in enumerate(self.pa_aggs):
             spec.aggs[i].type = t
             spec.aggs[i].column_id = max(cid, 0)
-            spec.aggs[i].log2m = log2m
+            spec.aggs[i].log2m = log2m if t != L.PA_AGG_MOMENTS else 0
             if t == L.PA_AGG_SUM and names.get(cid) in self.wide_sum_columns:
                 spec.aggs[i].flags = L.PA_AGGF_WIDE_SUM
             time_dict = t in TIME_ROW_AGGS and self.segs[0].column(names[cid]).has_dictionary
@@ -640,6 +674,20 @@ class GpuQueryExecutor:
             es = T.fill_spec(self.programs, [ids[c] for c in self.expr_columns],
                              [-2 - cid if cid <= -2 else -1 for _, cid, _ in self.pa_aggs], self.group_by_expr)
             L.check(lib.pa_query_set_expressions(self.handle, ctypes.byref(es)), "pa_query_set_expressions")
+        if any(t == L.PA_AGG_MOMENTS for t, _, _ in self.pa_aggs):
+            ms = L.MomentsSpec()
+            for i in range(L.PA_MAX_AGGS):
+                ms.second_column[i] = -1
+            for i, (t, cid, cid2) in enumerate(self.pa_aggs):
+                if t != L.PA_AGG_MOMENTS:
+                    continue
+                ms.second_column[i] = cid2
+                form, pivot = self.moments.get((names[cid], names[cid2] if cid2 >= 0 else None), (L.PA_MOMENTS_FORM_AUTO, None))
+                ms.form[i] = int(form)
+                if pivot is not None and cid2 < 0:
+                    ms.has_pivot[i] = 1
+                    ms.pivot[i] = float(pivot)
+            L.check(lib.pa_query_set_moments(self.handle, ctypes.byref(ms)), "pa_query_set_moments")
         if self.dev_filters:
             fs = L.AggFilterSpec()
             fs.num_filters = len(self.dev_filters)
@@ -692,10 +740,10 @@ class GpuQueryExecutor:
         try:
             L.check(lib.pa_query_prepare(self.handle), "pa_query_prepare")
         except L.PinotAmdError as e:
-            with_time = any(a.function in Q.WITH_TIME_FUNCTIONS for a in q.aggregations)
+            with_time = any(a.function in Q.WITH_TIME_FUNCTIONS + Q.MOMENT_FUNCTIONS for a in q.aggregations)
             if (self.dev_filters or self.exprs or with_time) and getattr(e, "code", 0) == L.PA_EUNSUPPORTED:
-                # (what the library refuses of a query with aggregation filters, transform expressions or
-                # FIRSTWITHTIME / LASTWITHTIME)
+                # (what the library refuses of a query with aggregation filters, transform expressions,
+                # FIRSTWITHTIME / LASTWITHTIME or VAR / STDDEV / COVAR)
                 raise UnsupportedQuery(str(e)) from None
             raise
         self.num_keys = int(lib.pa_query_num_keys(self.handle))
@@ -709,6 +757,48 @@ class GpuQueryExecutor:
         for gd in self.global_dicts:
             self.strides.append(s)
             s *= len(gd) if gd is not None else 1
+
+    def _check_moments(self, a):
+        """What VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP / COVAR_POP / COVAR_SAMP take here (DESIGN.md "Moments",
+        limits); the key-space limits are the library's (pa_query_prepare: PA_EUNSUPPORTED)."""
+        fn = a.function
+        if a.filter is not None:
+            raise UnsupportedQuery("%s with a FILTER (WHERE ...) clause" % fn)
+        if any(b.filter is not None for b in self.query.aggregations):
+            raise UnsupportedQuery("%s in a query with aggregation filters" % fn)
+        if str(self.query.options.get("enableNullHandling", "false")).lower() == "true":
+            raise UnsupportedQuery("%s with null handling" % fn)
+        for c in (a.column,) + ((a.column2,) if fn in Q.COVARIANCE_FUNCTIONS else ()):
+            if isinstance(c, Q.Expr):
+                raise UnsupportedQuery("%s over a transform expression as its argument" % fn)
+            for sg in self.segs:
+                col = sg.column(c)
+                if not col.single_value:
+                    raise UnsupportedQuery("%s over the multi-value column %s" % (fn, c))
+                if col.data_type not in ("INT", "LONG", "FLOAT", "DOUBLE"):
+                    raise UnsupportedQuery("%s over the %s column %s" % (fn, col.data_type, c))
+
+    def fetch_moments(self, pi, num_groups, stream=None):
+        """The tuples of VAR / STDDEV / COVAR accumulator `pi` for the groups the last fetch_arrays returned, in its order
+        (pa_query_fetch_moments): a list of VarianceTuple, or of CovarianceTuple for a covariance. Synchronises `stream`."""
+        n = int(num_groups)
+        count = np.zeros(max(n, 1), dtype=np.int64)
+        vals = np.zeros((3, max(n, 1)), dtype=np.float64)
+        if n:
+            ptrs = (ctypes.c_void_p * 3)(*[vals[c].ctypes.data for c in range(3)])
+            L.check(L.lib().pa_query_fetch_moments(self.handle, stream, pi, n, count.ctypes.data, ptrs),
+                    "pa_query_fetch_moments")
+        c_, v0, v1, v2 = count[:n].tolist(), vals[0, :n].tolist(), vals[1, :n].tolist(), vals[2, :n].tolist()
+        if self.pa_aggs[pi][2] >= 0:
+            return [CovarianceTuple(v0[r], v1[r], v2[r], c_[r]) for r in range(n)]
+        return [VarianceTuple(c_[r], v0[r], v1[r]) for r in range(n)]
+
+    def moments_form(self, pi):
+        """(form, pivot) the library uses for VAR / STDDEV / COVAR accumulator `pi` (pa_query_moments_form)."""
+        form, pivot = ctypes.c_int32(), ctypes.c_double()
+        L.check(L.lib().pa_query_moments_form(self.handle, pi, ctypes.byref(form), ctypes.byref(pivot)),
+                "pa_query_moments_form")
+        return int(form.value), float(pivot.value)
 
     def _check_with_time(self, a):
         """What FIRSTWITHTIME / LASTWITHTIME takes here (DESIGN.md "First / last with time", limits); the key-space
@@ -831,7 +921,7 @@ class GpuQueryExecutor:
                                     8: "lds_dense", 9: "lds_dense", 10: "lds_dense", 11: "lds_dense", 12: "lds_dense",
                                     14: "lds_dense", 15: "lds_dense", 128: "select", 129: "distinct",
                                     130: "distinct", 131: "filtered", 132: "filtered", 133: "expr", 134: "expr",
-                                    135: "time_rows", 136: "time_rows"}[code]
+                                    135: "time_rows", 136: "time_rows", 137: "moments", 138: "moments"}[code]
         out["plan"]["variant"] = STRATEGY_VARIANTS.get(code, str(code))
         out["plan"]["eager_literals"] = int(L.lib().pa_query_num_eager_literals(self.handle))
         out["plan"]["lane_major"] = int(L.lib().pa_query_lane_major(self.handle))
@@ -846,6 +936,9 @@ class GpuQueryExecutor:
         # FIRSTWITHTIME / LASTWITHTIME accumulators: {accumulator index: 1 = packed, 2 = wide} (pa_query_time_row_form)
         out["plan"]["time_row_form"] = {i: int(L.lib().pa_query_time_row_form(self.handle, i))
                                         for i, (t, _, _) in enumerate(self.pa_aggs) if t in TIME_ROW_AGGS}
+        # VAR / STDDEV / COVAR accumulators: {accumulator index: (form, pivot)} (pa_query_moments_form)
+        out["plan"]["moments_form"] = {i: self.moments_form(i)
+                                       for i, (t, _, _) in enumerate(self.pa_aggs) if t == L.PA_AGG_MOMENTS}
         return out
 
     def fetch_arrays(self, stream=None, pooled=False, trim_spec=None):
@@ -875,8 +968,9 @@ class GpuQueryExecutor:
                     o = alloc(i, cap << log2m, np.uint8)
                 elif t == L.PA_AGG_DISTINCTCOUNT:
                     o = alloc(i, cap * self._presence_stride(i), np.uint8)
-                elif t == L.PA_AGG_VALUE_HISTOGRAM or t in TIME_ROW_AGGS:
-                    # (pa_query_fetch writes nothing: fetch_histograms / percentiles read the bins, fetch_time_rows the rows)
+                elif t == L.PA_AGG_VALUE_HISTOGRAM or t in TIME_ROW_AGGS or t == L.PA_AGG_MOMENTS:
+                    # (pa_query_fetch writes nothing: fetch_histograms / percentiles read the bins, fetch_time_rows the rows,
+                    # fetch_moments the tuples)
                     outs.append(None)
                     continue
                 else:
@@ -1196,6 +1290,7 @@ class GpuQueryExecutor:
                 key_cols[j] = [T.DoubleKey(v) for v in key_cols[j]]
         cols = []  # one python list per query aggregation
         hists = {}
+        moments = {}  # VAR / STDDEV / COVAR: one fetch per accumulator
         # FIRSTWITHTIME / LASTWITHTIME: one fetch per accumulator, over the union of its value columns + the time column
         time_rows = {}
         for a, pi in zip(q.aggregations, self.agg_map):
@@ -1242,6 +1337,10 @@ class GpuQueryExecutor:
                 if pi not in hists:
                     hists[pi] = self.fetch_histograms(pi, n, stream)
                 cols.append(hists[pi])
+            elif a.function in Q.MOMENT_FUNCTIONS:
+                if pi not in moments:
+                    moments[pi] = self.fetch_moments(pi, n, stream)
+                cols.append(moments[pi])
             elif a.function in Q.WITH_TIME_FUNCTIONS:
                 segs_, vals_ = time_rows[pi]
                 stored = self.with_time_stored[a.column]  # (from the plan: a placeholder plan leaves no segment here)
@@ -1302,7 +1401,7 @@ STRATEGY_VARIANTS = {0: "lds", 1: "global", 2: "partitioned", 4: "lane", 5: "lan
                      8: "gdense4", 9: "gdense8", 10: "gdense12", 11: "gdense_rs12", 12: "gdense_rs8", 14: "gdense_lm8",
                      15: "gdense_lm16", 128: "select", 129: "distinct_lds", 130: "distinct_global",
                      131: "filtered_lds", 132: "filtered_global", 133: "expr_lds", 134: "expr_global",
-                     135: "time_rows_lds", 136: "time_rows_global"}
+                     135: "time_rows_lds", 136: "time_rows_global", 137: "moments_lds", 138: "moments_global"}
 TIME_ROW_AGGS = (L.PA_AGG_LAST_ROW_BY_TIME, L.PA_AGG_FIRST_ROW_BY_TIME)
 
 
@@ -1592,6 +1691,10 @@ def _empty_value(a):
     fn = Q.base_function(a.function)
     if fn in Q.WITH_TIME_FUNCTIONS:
         return with_time_default(fn, a.data_type)
+    if fn in Q.VARIANCE_FUNCTIONS:  # (extractAggregationResult of an empty holder)
+        return VarianceTuple(0, 0.0, 0.0)
+    if fn in Q.COVARIANCE_FUNCTIONS:
+        return CovarianceTuple(0.0, 0.0, 0.0, 0)
     return ({"COUNT": 0, "SUM": 0.0, "MIN": float("inf"), "MAX": float("-inf")}.get(fn) if fn in
             ("COUNT", "SUM", "MIN", "MAX") else
             AvgPair(0.0, 0) if fn == "AVG" else

@@ -493,6 +493,7 @@ def projected_columns(query):
     for a in query.aggregations:
         Q.item_columns(a.column, cols)
         Q.item_columns(a.time_column, cols)  # (FIRSTWITHTIME / LASTWITHTIME: 7 x docs, LastWithTimeQueriesTest.java:225)
+        Q.item_columns(a.column2, cols)  # (COVARPOP / COVARSAMP: 8 covariances over 6 columns, StatisticalQueriesTest.java:330)
     return len(cols)
 
 

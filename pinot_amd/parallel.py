@@ -32,6 +32,9 @@ SECTION_OP = {
     # holds it: not element-wise reducible (refuse_time_rows raises before any collective)
     L.PA_ACC_TIME_ROW_U64: None,
     L.PA_ACC_TIME_MAX_I64: None,
+    # VAR / STDDEV / COVAR moment sums: every word is a sum (the ranks agree on form and pivot: table_layout)
+    L.PA_ACC_MOM_I64: dist.ReduceOp.SUM,
+    L.PA_ACC_MOM_F64: dist.ReduceOp.SUM,
 }
 SECTION_DTYPE = {
     L.PA_ACC_COUNT_U64: torch.int64,
@@ -48,6 +51,8 @@ SECTION_DTYPE = {
     L.PA_ACC_KEYS_I64: torch.int64,
     L.PA_ACC_TIME_ROW_U64: torch.int64,
     L.PA_ACC_TIME_MAX_I64: torch.int64,
+    L.PA_ACC_MOM_I64: torch.int64,
+    L.PA_ACC_MOM_F64: torch.float64,
 }
 # identity of each per-key section (what pa_query_reset leaves in an empty slot)
 SECTION_IDENTITY = {
@@ -283,6 +288,61 @@ def wide_sum_columns_local(query, segments):
     return out
 
 
+def moments_local(query, segments):
+    """Per VAR / STDDEV / COVAR accumulator of the query ("column" or "column|second column"), what this rank's segments
+    say about its form and pivot: [every argument column is INT / LONG with all values inside int32 (the library's
+    integer form: Column::fits_int32), the first column's smallest and largest value as doubles (NaN ignored; None
+    without a value)]. Expression arguments are left to the executor's refusal."""
+    out = {}
+    for a in query.aggregations:
+        if a.function not in MOMENT_FUNCTIONS or isinstance(a.column, Expr) or isinstance(a.column2, Expr):
+            continue
+        key = a.column if a.column2 is None else "%s|%s" % (a.column, a.column2)
+        if key in out:
+            continue
+        integer, lo, hi = True, None, None
+        for ci, name in enumerate([a.column] + ([a.column2] if a.column2 is not None else [])):
+            for s in segments:
+                c = s.column(name)
+                if c.data_type not in ("INT", "LONG", "FLOAT", "DOUBLE") or not c.single_value:
+                    integer = False  # (the executor refuses the query)
+                    continue
+                v = np.asarray(c.dictionary if c.has_dictionary else c.raw_values)
+                if c.data_type in ("INT", "LONG"):
+                    if len(v) and (int(v.min()) < -(1 << 31) or int(v.max()) >= (1 << 31)):
+                        integer = False
+                else:
+                    integer = False
+                if ci == 0:
+                    v = v.astype(np.float64)
+                    v = v[~np.isnan(v)]
+                    if len(v):
+                        lo = float(v.min()) if lo is None else min(lo, float(v.min()))
+                        hi = float(v.max()) if hi is None else max(hi, float(v.max()))
+        out[key] = [bool(integer), lo, hi]
+    return out
+
+
+def moments_agreed(gathered):
+    """{(column, second column or None): (form, pivot or None)} from every rank's moments_local: the integer form only
+    where every rank can keep it; the double form's variance pivot is the midpoint of the smallest and largest value any
+    rank holds (0 where that is not finite), as the library computes it over one rank's segments."""
+    out = {}
+    for key in sorted(set().union(*[set(g) for g in gathered])):
+        recs = [g[key] for g in gathered if key in g]
+        integer = all(r[0] for r in recs)
+        los = [r[1] for r in recs if r[1] is not None]
+        his = [r[2] for r in recs if r[2] is not None]
+        col, _, col2 = key.partition("|")
+        pivot = None
+        if not integer and not col2:
+            pivot = min(los) / 2 + max(his) / 2 if los else 0.0
+            if not np.isfinite(pivot):
+                pivot = 0.0
+        out[(col, col2 or None)] = (L.PA_MOMENTS_FORM_INTEGER if integer else L.PA_MOMENTS_FORM_DOUBLE, pivot)
+    return out
+
+
 def hash_keys_bound_local(query, segments):
     """The hashed key space's key bound of these segments (pa_plan.hip plan_key_space): every doc a key, or twice the
     values of a multi-value group-by column."""
@@ -308,14 +368,16 @@ class TableLayout:
     hash_keys_bound: int = 0                         # the largest rank's hashed key bound (equal tables everywhere)
     schema: dict = field(default_factory=dict)       # column -> (data type, has dictionary, single value): lets a rank
                                                      # whose segments are all empty plan the same accumulator block
+    moments: dict = field(default_factory=dict)      # VAR / STDDEV / COVAR: (column, second column or None) -> (form,
+                                                     # pivot or None) every rank passes to pa_query_set_moments
 
     def executor_kwargs(self):
         """Keyword arguments of GpuQueryExecutor that make every rank's accumulator block line up."""
         return dict(table_dicts=self.dicts, wide_sum_columns=self.wide, value_dicts=self.value_dicts,
-                    hash_keys_bound=self.hash_keys_bound, schema=self.schema)
+                    hash_keys_bound=self.hash_keys_bound, schema=self.schema, moments=self.moments)
 
 
-from .query import DISTINCT_SET_FUNCTIONS as DISTINCT_FUNCTIONS, Expr, PERCENTILE_FUNCTIONS, query_columns  # noqa: E402
+from .query import DISTINCT_SET_FUNCTIONS as DISTINCT_FUNCTIONS, Expr, MOMENT_FUNCTIONS, PERCENTILE_FUNCTIONS, query_columns  # noqa: E402
 
 
 def _encode_record(rec):
@@ -391,14 +453,15 @@ def table_layout(query, segments, group=None):
     """Everything the ranks of one multi-GPU query must agree on before building their executors, in one all-gather:
     the table-wide dictionary of every dictionary-encoded group-by column (the union over all ranks' segments: the
     value-keyed combine of GroupByCombineOperator needs the same key id for the same value on every GPU), the SUM
-    columns that need the wide accumulator on some rank, the table-wide value dictionary of every DISTINCTCOUNT column
+    columns that need the wide accumulator on some rank, the form and pivot of every VAR / STDDEV / COVAR accumulator
+    (integer only where every rank's columns stay inside int32; the pivot from every rank's minimum and maximum), the table-wide value dictionary of every DISTINCTCOUNT column
     (presence byte j must mean the same value on every rank before the uint8-MAX reduce ORs them) and the largest
     rank's hashed key bound (every rank's hashed table then has the same slots). Returns a TableLayout; build every
     rank's executor with GpuQueryExecutor(..., **layout.executor_kwargs())."""
     refuse_time_rows(query)
     segments = [s for s in segments if s.num_docs > 0]  # (empty segments hold no columns: SegmentColumnarIndexCreator)
     local = {"dicts": {}, "vals": {}, "wide": sorted(wide_sum_columns_local(query, segments)),
-             "hb": hash_keys_bound_local(query, segments), "schema": {}}
+             "hb": hash_keys_bound_local(query, segments), "schema": {}, "mom": moments_local(query, segments)}
     for s in segments:
         for name in query_columns(query):
             c = s.column(name)
@@ -426,6 +489,7 @@ def table_layout(query, segments, group=None):
         out.value_dicts[name] = np.unique(np.concatenate([g["vals"][name] for g in gathered if name in g["vals"]]))
     out.wide = sorted(set().union(*[set(g["wide"]) for g in gathered]))
     out.hash_keys_bound = max(int(g["hb"]) for g in gathered)
+    out.moments = moments_agreed([g["mom"] for g in gathered])
     for g in gathered:
         for name, meta in g["schema"].items():
             out.schema.setdefault(name, tuple(meta))

@@ -19,7 +19,9 @@ Comparison predicates become RangePredicate exactly as the reference's RequestCo
 (pinot-common/.../request/context/RequestContextUtils.java: >, >=, <, <=, BETWEEN -> RANGE).
 Aggregations: COUNT(*), SUM, MIN, MAX, AVG, MINMAXRANGE, DISTINCTCOUNT, DISTINCTSUM, DISTINCTAVG, DISTINCTCOUNTHLL(col[, log2m]), DISTINCTCOUNTRAWHLL(col[, log2m]) and their *MV
 forms; PERCENTILE<digits>(col), PERCENTILE<digits>MV(col), PERCENTILE(col, p), PERCENTILEMV(col, p);
-FIRSTWITHTIME(dataCol, timeCol, 'dataType') and LASTWITHTIME(...) (any case, with or without underscores).
+FIRSTWITHTIME(dataCol, timeCol, 'dataType') and LASTWITHTIME(...) (any case, with or without underscores);
+VAR_POP / VAR_SAMP / STDDEV_POP / STDDEV_SAMP (col) and COVAR_POP / COVAR_SAMP (col1, col2) (any case, with or without
+underscores).
 """
 import decimal
 import re
@@ -183,6 +185,17 @@ _DATA_TYPES = ("INT", "LONG", "FLOAT", "DOUBLE", "BIG_DECIMAL", "BOOLEAN", "TIME
                "MAP", "LIST", "UNKNOWN")
 
 
+# VarianceAggregationFunction (VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP: the intermediate result is engine.VarianceTuple)
+# and CovarianceAggregationFunction (COVARPOP / COVARSAMP: engine.CovarianceTuple), factory cases
+# AggregationFunctionFactory.java:413-428; the functions of one family over the same argument(s) differ only in
+# extractFinalResult
+VARIANCE_FUNCTIONS = ("VARPOP", "VARSAMP", "STDDEVPOP", "STDDEVSAMP")
+COVARIANCE_FUNCTIONS = ("COVARPOP", "COVARSAMP")
+MOMENT_FUNCTIONS = VARIANCE_FUNCTIONS + COVARIANCE_FUNCTIONS
+# the names in the constructors' messages (VarianceAggregationFunction.getFunctionName)
+_VARIANCE_LABEL = {"VARPOP": "VAR_POP", "VARSAMP": "VAR_SAMP", "STDDEVPOP": "STD_DEV_POP", "STDDEVSAMP": "STD_DEV_SAMP"}
+
+
 def java_double_string(x):
     """Double.toString of a finite double: the shortest digits that round-trip (Python's repr gives the same digits),
     plain notation from 1e-3 up to 1e7, computerized scientific notation (1.0E-5) outside."""
@@ -301,6 +314,7 @@ class Aggregation:
     filter: object = None      # AGG(col) FILTER (WHERE filter): the filter tree, as written (no optimizer rewrite)
     time_column: object = None  # FIRSTWITHTIME / LASTWITHTIME: the time column's name (or the Expr written there)
     data_type: str = ""        # FIRSTWITHTIME / LASTWITHTIME: the declared type, upper case (WITH_TIME_TYPES)
+    column2: object = None     # COVARPOP / COVARSAMP: the second argument (a column's name, or the Expr written there)
 
     @property
     def result_name(self):
@@ -327,6 +341,9 @@ class Aggregation:
             # lastwithtime(intColumn,timestampColumn,'INT') (LastWithTimeQueriesTest.java:239-244): no spaces, the type
             # literal upper-cased in quotes
             return "%s(%s,%s,'%s')" % (self.function.lower(), self.column, self.time_column, self.data_type)
+        if self.function in COVARIANCE_FUNCTIONS:
+            # CovarianceAggregationFunction.getResultColumnName (:72-74): covarpop(x,y), no space
+            return "%s(%s,%s)" % (self.function.lower(), self.column, self.column2)
         return "%s(%s)" % (self.function.lower(), self.column)
 
 
@@ -377,6 +394,7 @@ class Query:
         for a in self.aggregations:
             item_columns(a.column, cols)
             item_columns(a.time_column, cols)
+            item_columns(a.column2, cols)
             filter_columns(a.filter, cols)
         if self.is_selection or self.is_distinct:
             cols.update(self.select_columns)
@@ -510,6 +528,8 @@ class _Parser:
             return self.percentile(fn)
         if fn.replace("_", "") in WITH_TIME_FUNCTIONS:
             return self.with_time(fn.replace("_", ""))
+        if fn.replace("_", "") in MOMENT_FUNCTIONS:
+            return self.moments(fn.replace("_", ""))
         col = self.item()
         log2m = DEFAULT_HLL_LOG2M
         if self.op(","):
@@ -587,6 +607,24 @@ class _Parser:
         """The next tokens start an aggregation: name( where the name is no transform function."""
         tok, nxt = self.peek(), self.peek(1)
         return tok[0] == "id" and nxt == ("op", "(") and tok[1].replace("_", "").lower() not in TRANSFORM_NAMES
+
+    def moments(self, fn):
+        """VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP take exactly one argument (verifySingleArgument,
+        VarianceAggregationFunction.java:51), COVARPOP / COVARSAMP two (CovarianceAggregationFunction.java:57-61)."""
+        args = []
+        if not self.op(")"):
+            while True:
+                args.append(self.item())
+                if not self.op(","):
+                    break
+            self.expect_op(")")
+        if fn in VARIANCE_FUNCTIONS:
+            if len(args) != 1:
+                raise ValueError("%s expects 1 argument, got: %d" % (_VARIANCE_LABEL[fn], len(args)))
+            return Aggregation(fn, args[0])
+        if len(args) != 2:
+            raise ValueError("%s expects 2 arguments, got: %d" % (fn, len(args)))
+        return Aggregation(fn, args[0], column2=args[1])
 
     def with_time(self, fn):
         """AggregationFunctionFactory.java:224-252 (FIRSTWITHTIME) and :324-350 (LASTWITHTIME): exactly three arguments,
@@ -853,7 +891,7 @@ def query_columns(query):
             names.append(f.column)
     if query.filter is not None:
         walk(query.filter)
-    for n in list(query.group_by) + [c for a in query.aggregations for c in (a.column, a.time_column) if c] + \
+    for n in list(query.group_by) + [c for a in query.aggregations for c in (a.column, a.time_column, a.column2) if c] + \
             (list(query.select_columns) if query.is_distinct else []):
         item_columns(n, names)
     for a in query.aggregations:

@@ -4,7 +4,9 @@
                          (AggregationFunction.merge: COUNT/SUM +, MIN min, MAX max, AVG pair +, HLL addAll,
                          MINMAXRANGE pair min/max, DISTINCTCOUNT / DISTINCTSUM / DISTINCTAVG set union,
                          PERCENTILE addAll = value histogram counts added,
-                         FIRSTWITHTIME / LASTWITHTIME the pair of the earlier / later time, the first argument on a tie)
+                         FIRSTWITHTIME / LASTWITHTIME the pair of the earlier / later time, the first argument on a tie,
+                         VARPOP / VARSAMP / STDDEVPOP / STDDEVSAMP VarianceTuple.apply, COVARPOP / COVARSAMP
+                         CovarianceTuple.apply)
   server_trim          ~ IndexedTable.finish on the server (IndexedTable.java:149): with ORDER BY keep the top
                          max(limit*5, minServerGroupTrimSize) groups (GroupByUtils.getTableCapacity); without
                          ORDER BY keep `limit` groups (GroupByCombineOperator.java:63-73)
@@ -17,7 +19,7 @@ import math
 from functools import cmp_to_key
 
 from . import query as Q
-from .engine import AvgPair, IntermediateResult, MinMaxRangePair
+from .engine import AvgPair, CovarianceTuple, IntermediateResult, MinMaxRangePair, VarianceTuple
 from .hll import HyperLogLog
 
 
@@ -44,6 +46,16 @@ def merge_value(fn, a, b):
         return a if a.time >= b.time else b
     if fn == "FIRSTWITHTIME":  # FirstWithTimeAggregationFunction.merge (:227)
         return a if a.time <= b.time else b
+    if fn in Q.VARIANCE_FUNCTIONS:
+        # VarianceTuple.apply(VarianceTuple) (:46-55), in its order of operations: Chan et al.'s pairwise update
+        if b.count == 0:
+            return a
+        curr_avg = 0.0 if a.count == 0 else a.sum / a.count
+        delta = (b.sum / b.count) - curr_avg
+        m2 = a.m2 + (b.m2 + delta * delta * b.count * a.count / (b.count + a.count))
+        return VarianceTuple(a.count + b.count, a.sum + b.sum, m2)
+    if fn in Q.COVARIANCE_FUNCTIONS:  # CovarianceTuple.apply(CovarianceTuple) (:51-56)
+        return CovarianceTuple(a.sum_x + b.sum_x, a.sum_y + b.sum_y, a.sum_xy + b.sum_xy, a.count + b.count)
     raise ValueError(fn)
 
 
@@ -79,6 +91,27 @@ def final_value(fn, v):
         if fn == "DISTINCTSUM":
             return s
         return s / len(v) if len(v) else math.nan
+    if fn in Q.VARIANCE_FUNCTIONS:
+        # VarianceAggregationFunction.extractFinalResult (:228-248): DEFAULT_FINAL_RESULT = -inf for no doc, and for one
+        # doc under the sample forms
+        n = v.count
+        sample = fn in ("VARSAMP", "STDDEVSAMP")
+        if n == 0 or (sample and n - 1 == 0):
+            return -math.inf
+        var = v.m2 / (n - 1) if sample else v.m2 / n
+        if fn in ("STDDEVPOP", "STDDEVSAMP"):
+            return math.sqrt(var) if var >= 0 else math.nan  # (Math.sqrt: NaN for NaN and negatives)
+        return var
+    if fn in Q.COVARIANCE_FUNCTIONS:
+        # CovarianceAggregationFunction.extractFinalResult (:186-203); count * count is a long product in Java
+        n = v.count
+        if n == 0:
+            return -math.inf
+        if fn == "COVARSAMP":
+            if n - 1 == 0:
+                return -math.inf
+            return (v.sum_xy / (n - 1)) - (v.sum_x * v.sum_y) / _java_long(n * (n - 1))
+        return (v.sum_xy / n) - (v.sum_x * v.sum_y) / _java_long(n * n)
     if fn in Q.WITH_TIME_FUNCTIONS:
         # extractFinalResult: the pair's value; a 'BOOLEAN' pair holds the int (IntLongPair), the BOOLEAN result column
         # shows value != 0
@@ -86,6 +119,11 @@ def final_value(fn, v):
             return v.value != 0
         return v.value
     return v
+
+
+def _java_long(x):
+    """A Java long product: wraps at 64 bits."""
+    return ((int(x) + (1 << 63)) & ((1 << 64) - 1)) - (1 << 63)
 
 
 def _add_stat(a, b):

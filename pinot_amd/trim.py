@@ -45,6 +45,8 @@ def lower_order_by(query, agg_map, hashed=False):
             raise HostTrim("the query has aggregation filters")
         if a.function in Q.PERCENTILE_FUNCTIONS:
             raise HostTrim("the query has a PERCENTILE aggregation (value histogram)")
+        if a.function in Q.MOMENT_FUNCTIONS:
+            raise HostTrim("the query has a VAR / STDDEV / COVAR aggregation (moment sums)")
     if len(query.order_by) > MAX_TERMS:
         raise HostTrim("more than %d ORDER BY terms" % MAX_TERMS)
     terms = []
